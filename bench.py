@@ -2,7 +2,7 @@
 """bags/sec, forward+backward(+optimizer step) of DeformCrossTransMIL on bags of 10 000 instances x 512
 features (BASELINE.json metric), whole bags data-parallel over the GPUs of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,9 @@ per GPU: DeformCrossTransMIL forward (fc1 -> fusion -> LayerNorm -> 2-D deformab
 continuous position bias over a 100 x 100 token grid / 625 sampled keys -> pooler -> heads), cross-entropy +
 BatchLoss (gathered over ranks), backward, gradient all-reduce (RCCL), Adam step.  Inputs are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the line (the headline, with the HIP-event times of the two dominant
+kernels and the roofline figures derived from them).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
+Everything below runs only with --full.
 After the timed region, at N = 1 only: `nystrom[1].kernel_counters` (per kernel of the 4 x 10 000 bf16 Nystrom leg: time, matrix-pipe busy
 share, HBM bytes - three rocprofv3 --pmc child runs of `--nystrom-child`) and `roofline.traffic` from two child runs of this script under rocprofv3 --pmc (FETCH_SIZE,
 WRITE_SIZE; --no-traffic skips them), the Nystrom legs (extra key `nystrom`; --no-nystrom), the CPU baseline (--no-cpu-baseline) and three more
@@ -278,6 +281,35 @@ def timed_steps(step, steps, warmup):
             "host_bound": bool(t_enq > 0.9 * dt)}, dt
 
 
+DUMP_SAMPLE = 1 << 20               # elements kept of one larger array
+DUMP_BUDGET = 64 << 20              # bytes written in all
+
+
+def dump_outputs(dirname, outputs, model):
+    """--dump-outputs: what the last timed step handed its caller - the loss, the model's outputs and every parameter's gradient
+    (`grad.<parameter name>`) - as DIR/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is replaced by the
+    elements at DUMP_SAMPLE fixed flat indices (sorted, from a permutation seeded with 0): the same in every run of the same
+    arguments, so that two builds can be compared output for output.
+    The inputs, and the parameters every timed step starts from (make_adam), are identical from run to run; what still differs is
+    rounding: the weight gradients reduced with float atomics (Determinism), ~1e-6 of each array's scale."""
+    import numpy as np
+    arrays = dict(outputs)
+    arrays.update(("grad." + k, p.grad) for k, p in model.named_parameters() if p.grad is not None)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            a = a.reshape(-1)[idx]
+        host[name] = a.numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def kernel_event_sum(kt, steps):
     """ms per step spent in the kernels the package brackets with HIP events (the fused attention family)."""
     return sum(n * ms for n, ms, _ in kt.values()) / max(steps, 1)
@@ -307,10 +339,14 @@ def nystrom_leg(pkg, dev, B, n, dtype=torch.bfloat16, steps=10, warmup=10):
 
 
 def make_adam(params, capturable=False):
-    """torch.optim.Adam as the reference configures it (lr / weight decay of config_mine.yaml:41-47 scaled down for a synthetic step); the
-    fused implementation (one multi-tensor launch instead of seven) where this torch build has it - SMML_ADAM=foreach selects the other."""
+    """torch.optim.Adam as the reference configures it (weight decay of config_mine.yaml:41-47), with learning rate 0: the update runs in
+    full (moments, bias correction, weight decay, the parameter write) and leaves every parameter where set-up put it, so each timed
+    step computes from the same inputs.  A moving synthetic model would make the last step's results depend on every earlier step's:
+    the weight gradients reduced with float atomics differ in the last bits from run to run (Determinism) and the steps
+    carry that forward (measured: up to O(1) in some gradients after ten steps).  The fused implementation (one multi-tensor launch
+    instead of seven) where this torch build has it - SMML_ADAM=foreach selects the other."""
     params = list(params)
-    kw = dict(lr=1e-4, weight_decay=0.1, capturable=capturable)
+    kw = dict(lr=0.0, weight_decay=0.1, capturable=capturable)
     if os.environ.get("SMML_ADAM", "fused") == "fused":
         try:
             return torch.optim.Adam(params, fused=True, **kw)
@@ -500,9 +536,12 @@ def main():
     ap.add_argument("--bags", type=int, default=8, help="bags per GPU per step (the reference trains with batch_size 8 per rank, config/config_mine.yaml:38)")
     ap.add_argument("--grid", type=int, default=100, help="token grid side (N = grid^2)")
     ap.add_argument("--in-dim", type=int, default=512, help="bag feature width")
+    ap.add_argument("--full", action="store_true", help="after the headline, at N = 1: the extra legs, the live HBM traffic and the CPU baseline "
+                    "(each --no-... option below skips one of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--deform-table", nargs="?", const=True, default=False, help="measurement switch (with --deform-dtype): the headline step with the tabulated position "
-                    "bias (approximate mode; `--deform-table forward`: table in the forward only, exact backward; the default run reports both in the extra keys `deform16_table` / `deform16_tabfwd`)")
+                    "bias (approximate mode; `--deform-table forward`: table in the forward only, exact backward; a --full run reports both in the extra keys `deform16_table` / `deform16_tabfwd`)")
     ap.add_argument("--no-deform16", action="store_true", help="skip the 16-bit-compute-mode leg of the headline step (extra key `deform16`, not part of `value`)")
     ap.add_argument("--no-nystrom", action="store_true", help="skip the Nystrom legs (extra key `nystrom`, not part of `value`)")
     ap.add_argument("--no-dp-overhead", action="store_true", help="skip the leg that wraps the headline step in a one-rank RCCL group (extra key `data_parallel_at_world_1`)")
@@ -511,7 +550,7 @@ def main():
     ap.add_argument("--nystrom-child", default=None, help="internal: B,n,dtype - run that Nystrom leg alone (3 + 3 steps) and exit (profiled by the parent)")
     ap.add_argument("--deform-dtype", default=None, choices=[None, "bf16", "fp16"],
                     help="measurement switch: run the HEADLINE step itself with the fused attention core in its 16-bit compute mode (the "
-                         "default line stays fp32-grade; the default run reports the 16-bit step in the extra key `deform16`)")
+                         "default line stays fp32-grade; a --full run reports the 16-bit step in the extra key `deform16`)")
     ap.add_argument("--graph", action="store_true", help="one GPU only: capture the step in a hipGraph and time replays (the per-kernel "
                     "HIP-event times of `roofline` then come from the eager warm-up steps)")
     ap.add_argument("--dp-child", action="store_true", help=argparse.SUPPRESS)
@@ -567,13 +606,19 @@ def main():
     omic = torch.relu(pkg.synth.normal((B, 128), 42 + rank, "bench:omicvec")).to(dev)
     label = torch.randint(0, 4, (B,), generator=torch.Generator().manual_seed(rank)).to(dev)
 
-    def step():
+    last = {}
+
+    def step(keep=None):
         enc, logits, _, omic_t, vgrid = model(path, omic)
         loss = torch.nn.functional.cross_entropy(logits, label) + torch.sum(bloss(omic_t, vgrid))
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
+        if keep is not None:               # the last timed step, for --dump-outputs (detached: no autograd graph outlives the step)
+            keep.update(loss=loss.detach(), logits=logits.detach(), encoded=enc.detach(), omic_tiled=omic_t.detach(), vgrid=vgrid.detach())
         return loss
+
+    dump = a.dump_outputs is not None and rank == 0
 
     def fence():
         if world > 1:
@@ -593,7 +638,7 @@ def main():
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                step()
+                step(last if dump else None)    # the captured outputs are rewritten by every replay
         torch.cuda.current_stream().wait_stream(side)
         graph.replay()
         fence()
@@ -611,8 +656,8 @@ def main():
         fence()
         Fh.TIMER.enabled = True
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step()
+        for i in range(a.steps):
+            step(last if dump and i == a.steps - 1 else None)
         fence()
         dt = time.perf_counter() - t0
         Fh.TIMER.enabled = False
@@ -663,7 +708,7 @@ def main():
             ach = abytes / (ms * 1e-3) / 1e9
             flop = pairs * (CPB_FWD_FLOP_PER_PAIR + ATTN_FLOP_PER_PAIR)
             out["roofline"] = {"kernel": "deform_region_fwd_kernel<true>", "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": ach / HBM_PEAK_GBS, "traffic": None, "traffic_source": "not collected (--no-traffic, or N > 1)",
+                               "frac": ach / HBM_PEAK_GBS, "traffic": None, "traffic_source": "not collected (collected with --full at N = 1)",
                                "launches": n, "avg_ms": ms, "algorithmic_bytes_per_launch": abytes,
                                "reference_flops_view": {"flop_per_launch": flop, "achieved_TFLOPs": flop / (ms * 1e-3) / 1e12,
                                                         "frac_of_16bit_mfma_peak": flop / (ms * 1e-3) / 1e12 / F16_MFMA_PEAK_TFLOPS,
@@ -702,25 +747,23 @@ def main():
                                        "launches": n, "avg_ms": ms, "flop_per_launch": flop}
         if world > 1:
             out["data_parallel"] = dp_info               # what the collective backend saw + per-rank overlap counters: a SCALE run checks itself
-        # the headline is measured: persist it before anything else can go wrong (an extra leg must never cost the line)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_headline.json"), "w") as f:
-                f.write(json.dumps(out) + "\n")
-        except OSError:
-            pass
-        print("HEADLINE " + json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "ms_per_step")}), file=sys.stderr, flush=True)
+        if dump:
+            dump_outputs(a.dump_outputs, last, mil)
+        full = a.full and world == 1
+        if full:
+            # the headline is measured: print it before anything else can go wrong (an extra leg must never cost the line)
+            print("HEADLINE " + json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "ms_per_step")}), file=sys.stderr, flush=True)
         # everything below runs on a GPU the headline model no longer occupies
-        del step, model, mil, opt, bloss, path, omic, label
+        del step, model, mil, opt, bloss, path, omic, label, last
         if use_graph:
             del graph
         torch.cuda.empty_cache()
-        if world == 1 and not a.no_dp_overhead and not a.deform_dtype:
+        if full and not a.no_dp_overhead and not a.deform_dtype:
             try:
                 out["data_parallel_at_world_1"] = dp_overhead_leg(pkg, dev, B, S, in_dim, out["ms_per_step"])
             except Exception as e:
                 out["data_parallel_at_world_1"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_deform16 and not a.deform_dtype:
+        if full and not a.no_deform16 and not a.deform_dtype:
             # BASELINE config 4 as stated (bf16 compute) and its table variants: the same step with the fused core in its 16-bit mode
             for key, kw in (("deform16", {}), ("deform16_tabfwd", {"cpb_table": "forward"}), ("deform16_table", {"cpb_table": True})):
                 try:
@@ -728,7 +771,7 @@ def main():
                     out[key]["speedup_vs_fp32_line"] = out[key]["bags_per_s"] / out["value"]
                 except Exception as e:
                     out[key] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_nystrom:
+        if full and not a.no_nystrom:
             # the north_star's Nystrom target, driver-run: BASELINE config 2 shape and the N = 10 000 bag (not part of `value`);
             # timed BEFORE the PMC child runs below so that nothing of theirs can still be on the GPU
             out["nystrom"] = nystrom_legs(pkg, dev)
@@ -737,7 +780,7 @@ def main():
                     out["nystrom"][1]["kernel_counters"] = nystrom_kernel_counters(4, 10000, "bfloat16")
                 except Exception as e:
                     out["nystrom"][1]["kernel_counters"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and "roofline" in out:
+        if full and "roofline" in out:
             kname = "deform_region_fwd_kernel" if regions else "cpb_bwd_kernel"
             traffic, tsrc = None, "not collected (--no-traffic)"
             if not a.no_traffic:
@@ -749,7 +792,7 @@ def main():
                     traffic = measured_traffic(kname, B)
                     tsrc = f"replayed from profiles/{TRAFFIC_FILE} (rocprofv3 --pmc passes of this command, committed); live collection: {tsrc}"
             out["roofline"]["traffic"], out["roofline"]["traffic_source"] = traffic, tsrc
-        if world == 1 and not a.no_cpu_baseline:
+        if full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(pkg, in_dim, S)
             except Exception as e:                    # the GPU figures above are measured: a host-side failure must not lose the line

@@ -101,8 +101,12 @@ def test_host_layer_under_asan_and_ubsan(tmp_path):
     lib = bld.build_host_sanitized(verbose=False)
     script = tmp_path / "walk.py"
     script.write_text(textwrap.dedent(CHILD))
-    env = dict(os.environ, LD_PRELOAD=bld.SAN_RUNTIME, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    # the walk is host-only: on a machine with a GPU the entry points would initialise HIP, whose device allocations the ASan runtime
+    # intercepts (and fails); with no GPU visible the child sees what it sees on a machine without one.  The ASan runtime must come
+    # first in the preload list; whatever else is preloaded stays.
+    preload = ":".join(p for p in (bld.SAN_RUNTIME, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, str(script), lib, os.path.join(ROOT, "include", "smml.h")], capture_output=True, text=True, env=env, timeout=300)
     report = (r.stdout + r.stderr)
     assert r.returncode == 0 and "OK" in r.stdout, report[-4000:]

@@ -3,7 +3,7 @@
 set -u
 mkdir -p gpurun_out/r5
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-timeout -k 10 900 python bench.py > gpurun_out/r5/bench_b8.json 2> gpurun_out/r5/bench_b8.err || { echo "bench failed"; tail -5 gpurun_out/r5/bench_b8.err; exit 1; }
+timeout -k 10 900 python bench.py --full > profiles/r05_bench_b8.json || { echo "bench failed"; exit 1; }
 rm -rf gpurun_out/r5/prof
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r5/prof -- python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-nystrom --no-traffic --no-deform16 --no-dp-overhead > gpurun_out/r5/prof.log 2>&1
 echo "prof rc=$?"
