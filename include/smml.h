@@ -235,6 +235,32 @@ int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float*
                                     void* workspace, size_t workspace_bytes, int B, int N, int J, int H, float scale, float dropout_p,
                                     unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts);
 
+/* The 1-D sibling (csrc/cpb_regions1d.h): the MLP of DeformableAttention1D.py:69-98 (Linear(1, 32) - ReLU - Linear(32, 32) - ReLU -
+ * Linear(32, H/G)) is piecewise affine in ONE signed-log offset, with at most 1088 breakpoints.  smml_cpb_regions1d_build sorts them and
+ * tabulates per piece its ReLU pattern (D1 | D2 << 32) and (a, c) for each of the `outputs` (= H / G, 1 or 2) outputs, plus a uniform index
+ * grid over [-pmax, pmax] (pmax = 0: the span of the breakpoints; points outside the grid take an exact binary search - pmax is for speed
+ * only).  The forward / backward replace the per-pair MLP by a lookup + 2 FMAs, resp. by two fixed-point moments per piece and output.
+ * posdim = 1, signed-log offsets (opts->raw_distance must be 0), H / G in {1, 2}, J <= 16384, the fp32-grade core; no weights are
+ * passed: the tables hold them.  Results are those of smml_deform_attn_fwd_f32 / _bwd_f32 (posdim 1) to fp32 rounding.
+ *   tables: smml_cpb_regions1d_bytes() bytes, 256-byte aligned, built per forward call and handed unchanged to the backward.
+ *   region_ids [B, H, nst / 32, J, 32] uint16: the piece of every pair, per head (the heads of a group share it).
+ *   workspace of the backward: smml_deform_attn_region1d_bwd_workspace_bytes, 256-byte aligned.  A non-finite d score makes the six
+ *   parameter gradients NaN.  Every output is run-to-run identical. */
+size_t smml_cpb_regions1d_bytes(void);
+int smml_cpb_regions1d_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                             int outputs, float pmax, void* tables, size_t tables_bytes, void* stream);
+int smml_deform_attn_region1d_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const void* tables,
+                                      float* out, float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                      float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop,
+                                      void* stream, const SmmlDeformOpts* opts);
+size_t smml_deform_attn_region1d_bwd_workspace_bytes(int B, int N, int J, int H);
+int smml_deform_attn_region1d_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const void* tables,
+                                      const float* out, const float* dout, const float* lse, const float* logits_t,
+                                      const unsigned short* region_ids, float* dlogits_t, float* dq, float* dk, float* dv, float* dvs,
+                                      float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                                      size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p,
+                                      unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts);
+
 /* The same two entry points in the 16-bit compute modes of smml_deform_attn16_fwd / _bwd (dtype 0 = bf16, 1 = fp16: single-term operands on
  * the matrix pipe, scores saved as fp16 [B, H, nst / 32, J, 32], d scores as bf16): the position bias stays the fp32 lookup per linear
  * region, so it is MORE exact than the 16-bit per-pair MLP it replaces, and the launch pair costs about half of it.  Same conditions as

@@ -25,6 +25,7 @@
 // (DESIGN.md section 4 for the error bounds and the measurements behind them).
 #include "deform_common.h"
 #include "cpb_regions.h"
+#include "cpb_regions1d.h"
 
 namespace {
 
@@ -1424,6 +1425,124 @@ int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float*
   rc = region_bias_bwd_launch<float>("smml_deform_attn_region_bwd_f32", dlogits_t, region_ids, vs, gq, cp, tables, wsb, pl, B, N, J, H, nst, lcap, dvs,
                                      dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
   if (rc) return rc;
+  return SMML_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// position bias per linear piece, 1-D positions (cpb_regions1d.h): exact, signed-log offsets, H / G in {1, 2}
+// ------------------------------------------------------------------------------------------------
+size_t smml_cpb_regions1d_bytes(void) { return region1d_layout().total; }
+
+int smml_cpb_regions1d_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                             int outputs, float pmax, void* tables, size_t tables_bytes, void* stream) {
+  SMML_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && tables, "smml_cpb_regions1d_build: null pointer");
+  SMML_REQUIRE(outputs == 1 || outputs == 2, "smml_cpb_regions1d_build: outputs (heads per offset group) must be 1 or 2 (got %d)", outputs);
+  SMML_REQUIRE(pmax >= 0.f && pmax < 16.f, "smml_cpb_regions1d_build: pmax must be in [0, 16) (got %g)", (double)pmax);
+  SMML_REQUIRE(tables_bytes >= region1d_layout().total, "smml_cpb_regions1d_build: table buffer too small (%zu < %zu)", tables_bytes,
+               region1d_layout().total);
+  SMML_REQUIRE((reinterpret_cast<size_t>(tables) & 255) == 0, "smml_cpb_regions1d_build: table buffer must be 256-byte aligned");
+  region1d_build_launch(CpbParams{w1, b1, w2, b2, w3, b3}, outputs, pmax, tables, (hipStream_t)stream);
+  SMML_LAUNCH_CHECK("smml_cpb_regions1d_build");
+  return SMML_OK;
+}
+
+int smml_deform_attn_region1d_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const void* tables,
+                                      float* out, float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                      float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop,
+                                      void* stream, const SmmlDeformOpts* opts) {
+  int rc = check_region1d("smml_deform_attn_region1d_fwd_f32", B, N, J, H, G);
+  if (rc) return rc;
+  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_region1d_fwd_f32: dropout_p must be in [0, 1)");
+  SMML_REQUIRE(q && k && v && vs && gq && tables && out && lse, "smml_deform_attn_region1d_fwd_f32: null pointer");
+  SMML_REQUIRE((logits_t == nullptr) == (region_ids == nullptr),
+               "smml_deform_attn_region1d_fwd_f32: logits_t and region_ids are saved together (training) or not at all");
+  SMML_REQUIRE(!(opts && opts->raw_distance), "smml_deform_attn_region1d_fwd_f32: the piece tables are built for signed-log offsets");
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  const Region1DView rv = region1d_view(tables);
+  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B), block(256);
+  const int nst = smml_deform_attn_nst(N);
+  hipStream_t st = (hipStream_t)stream;
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+  if (region_ids)
+    hipLaunchKernelGGL(deform_region1d_fwd_kernel<true>, grid, block, 0, st, q, k, v, vs, gq, rv, out, lse, logits_t, region_ids, N, J, H,
+                       G, nst, scale, dc);
+  else
+    hipLaunchKernelGGL(deform_region1d_fwd_kernel<false>, grid, block, 0, st, q, k, v, vs, gq, rv, out, lse, logits_t, region_ids, N, J, H,
+                       G, nst, scale, dc);
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_fwd_f32");
+  return SMML_OK;
+}
+
+size_t smml_deform_attn_region1d_bwd_workspace_bytes(int B, int N, int J, int H) {
+  if (B <= 0 || N <= 0 || J <= 0 || H <= 0 || !deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS) return 0;
+  return region_bwd_plan(B, N, J, H).total;
+}
+
+int smml_deform_attn_region1d_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const void* tables,
+                                      const float* out, const float* dout, const float* lse, const float* logits_t,
+                                      const unsigned short* region_ids, float* dlogits_t, float* dq, float* dk, float* dv, float* dvs,
+                                      float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                                      size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p,
+                                      unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
+  static const char* fn = "smml_deform_attn_region1d_bwd_f32";
+  int rc = check_region1d(fn, B, N, J, H, G);
+  if (rc) return rc;
+  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0, 1)", fn);
+  SMML_REQUIRE(q && k && v && vs && gq && tables && out && dout && lse && logits_t && region_ids && dlogits_t && dq && dk && dv && dvs &&
+                   dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
+               "%s: null pointer", fn);
+  SMML_REQUIRE(!(opts && opts->raw_distance), "%s: the piece tables are built for signed-log offsets", fn);
+  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
+  SMML_REQUIRE(workspace_bytes >= pl.total, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, pl.total);
+  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  SMML_REQUIRE(pl.wpk >= 1, "%s: too many keys (%d)", fn, J);
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  hipStream_t st = (hipStream_t)stream;
+  const int nst = smml_deform_attn_nst(N);
+  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
+  dim3 block(256);
+  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
+  float* wsf = reinterpret_cast<float*>(workspace);
+  char* wsb = reinterpret_cast<char*>(workspace);
+  unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
+  unsigned* flag = amax + 1;                                 // non-finite d score seen (same zeroed 256-byte block)
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(wsb + pl.hist);
+  float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
+  double* part = reinterpret_cast<double*>(wsb + pl.part);
+  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);      // amax | flag | hist | grad
+  // pass 1: dS^T, dQ, max |dS|; pass 2: dK, dV - the kernels of the 2-D region path, unchanged
+  hipLaunchKernelGGL(deform_attn_bwd_dq_kernel, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits_t, dlogits_t, dq,
+                     wsf + wsl.rho, amax, N, J, H, nst, scale, dc);
+  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dq");
+  {
+    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
+    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
+    const int nslices = parts * H * B;
+    hipLaunchKernelGGL(deform_attn_bwd_dkv_kernel, dim3(((nslices + 7) / 8) * 8 * nkg), block, 0, st, q, dout, lse, logits_t, dlogits_t,
+                       wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
+    SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dkv");
+    const size_t n4 = (size_t)B * J * H * DH / 4;
+    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st, reinterpret_cast<const float4*>(wsf + wsl.dkp),
+                       reinterpret_cast<const float4*>(wsf + wsl.dvp), reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts,
+                       scale);
+    SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dkv_reduce");
+  }
+  // pass 3: position bias - d vs per pair, piece moments, then the dense pass to the six parameter gradients
+  const Region1DView rv = region1d_view(tables);
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+  hipLaunchKernelGGL(cpb_region1d_bwd_kernel, dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), 0, st, dlogits_t, region_ids, vs,
+                     gq, rv, amax, flag, hist, dvs_slab, N, J, H, G, nst, pl.nkb, pl.nkbg, pl.chunks, pl.wpk, pl.tiles_per_chunk, pl.kbits,
+                     pl.shift);
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/cpb");
+  const size_t n = (size_t)B * G * J;
+  hipLaunchKernelGGL(region1d_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dvs_slab, dvs, B, H, G, J, pl.chunks);
+  const Region1DTables rt = region1d_tables(const_cast<void*>(tables));
+  hipLaunchKernelGGL(region1d_final1_kernel, dim3(R1_GROUPS), dim3(256), 0, st, rt, hist, part);
+  hipLaunchKernelGGL(region1d_final2_kernel, dim3((R1G_N + 255) / 256), dim3(256), 0, st, part, amax, flag, pl.kbits - pl.shift, H / G, dw1,
+                     db1, dw2, db2, dw3, db3);
+  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/reduce");
   return SMML_OK;
 }
 

@@ -222,9 +222,16 @@ class DeformCrossAttention2D(nn.Module):
 class DeformCrossAttention1D(nn.Module):
     def __init__(self, *, dim, dim_head=64, heads=8, dropout=0., downsample_factor=4, offset_scale=None,
                  offset_groups=4, offset_kernel_size=6, cpb_log_distance=True, group_queries=False,
-                 group_key_values=False, true_1d_sampling: bool = False, compute_dtype=None, cpb_table: bool = False):
+                 group_key_values=False, true_1d_sampling: bool = False, compute_dtype=None, cpb_table: bool = False,
+                 cpb_regions: bool = False):
         super().__init__()
         self.true_1d_sampling = bool(true_1d_sampling)
+        # cpb_regions (off by default): the position bias per linear piece of its MLP (functional.deform_attention, csrc/cpb_regions1d.h) -
+        # signed-log offsets and the fp32-grade core only; heads // offset_groups must be 1 or 2 (checked at the call)
+        if cpb_regions and (compute_dtype is not None or cpb_table or not cpb_log_distance):
+            raise ValueError("cpb_regions (the 1-D piece path) takes signed-log offsets in the fp32-grade core: no compute_dtype, no cpb_table, "
+                             "cpb_log_distance=True")
+        self.cpb_regions = bool(cpb_regions)
         Fh._dtype16(compute_dtype)
         self.compute_dtype = compute_dtype
         if cpb_table and compute_dtype is None:
@@ -281,6 +288,9 @@ class DeformCrossAttention1D(nn.Module):
         if self.cpb_table:
             t = vgrid.shape[-1]
             tab = {"cpb_table": self.cpb_table, "cpb_table_pmax": Fh.table_pmax(1.0, 1.0 + 2.0 * self.offset_scale / max(t - 1, 1))}
+        if self.cpb_regions:              # |seq| <= 1, |vs| <= 1 + 2 offset_scale / (t - 1): the static signed-log bound of the table branch
+            t = vgrid.shape[-1]
+            tab = {"cpb_regions": True, "cpb_region_pmax": Fh.table_pmax(1.0, 1.0 + 2.0 * self.offset_scale / max(t - 1, 1))}
         o = Fh.deform_attention(q, k, v, vs, seq.contiguous(), *self.rel_pos_bias.tensors(), heads=H, groups=G,
                                 scale=self.scale, compute_dtype=self.compute_dtype, log_distance=self.cpb_log_distance, **tab,
                                 **_dropout_args(self, q.device))

@@ -8,7 +8,8 @@ sizes `_fc1`; the token count is taken from the bag instead of the hard-wired 25
 'fp16') selects the 16-bit compute mode of the fused attention core (BASELINE config 4), `args.deform_cpb_table` its table mode
 (the position-bias MLP evaluated on a grid once per call and interpolated per pair: include/smml.h).  `args.wrap_pad_to_square` (off by default;
 SURVEY.md 8(f) row 4) lets the 2-D branch take bags whose instance count is not a square: both token streams are
-wrap-padded to the next square as TransMIL does (models/mil.py:232-235), attended, and cropped back to N.
+wrap-padded to the next square as TransMIL does (models/mil.py:232-235), attended, and cropped back to N.  `args.deform1d_cpb_regions`
+(absent / False | True; the fp32-grade core only) evaluates the 1-D branch's position bias per linear piece of its MLP (csrc/cpb_regions1d.h).
 
 Differences in mechanism, not in values: the 2500x tiled omic matrix is never fed through a GEMM - the
 fusion layer is evaluated as path @ W[:, :C]^T + (omic @ W[:, C:]^T + b) with the second term broadcast
@@ -41,14 +42,14 @@ class FusionNet(nn.Module):
 
 
 class DeformCrossTransLayer(nn.Module):
-    def __init__(self, norm_layer=nn.LayerNorm, dim=128, grid_hw=None, compute_dtype=None, cpb_table=False):
+    def __init__(self, norm_layer=nn.LayerNorm, dim=128, grid_hw=None, compute_dtype=None, cpb_table=False, cpb_regions_1d=False):
         super().__init__()
         self.norm = norm_layer(dim)
         self.attn2d = DeformCrossAttention2D(dim=128, dim_head=64, heads=8, dropout=0.1, downsample_factor=4,
                                              offset_scale=4, offset_groups=8, offset_kernel_size=6, grid_hw=grid_hw,
                                              compute_dtype=compute_dtype, cpb_table=cpb_table)
         self.attn1d = DeformCrossAttention1D(dim=128, downsample_factor=4, offset_scale=2, offset_kernel_size=6,
-                                             compute_dtype=compute_dtype, cpb_table=cpb_table)
+                                             compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions_1d)
 
     def forward(self, x1, x2, attn_dim, return_vgrid):
         n = self.norm
@@ -88,7 +89,8 @@ class DeformCrossTransMIL(nn.Module):
         # 'bf16' | 'fp16' runs the fused attention core and its output projection in the 16-bit compute mode
         # `args.deform_cpb_table` (absent / False | 'forward' | True; with a 16-bit compute dtype only): position bias from a table of the MLP
         self.layer3 = DeformCrossTransLayer(dim=args.path_dim, grid_hw=getattr(args, "grid_hw", None), compute_dtype=cd,
-                                            cpb_table=getattr(args, "deform_cpb_table", False))
+                                            cpb_table=getattr(args, "deform_cpb_table", False),
+                                            cpb_regions_1d=bool(getattr(args, "deform1d_cpb_regions", False)))
         self.norm = nn.LayerNorm(args.path_dim)
         self._fc2 = nn.Linear(args.path_dim, self.n_classes)
         self.pooler = Pooler(args.path_dim)

@@ -921,6 +921,126 @@ def cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax: float, tables: Optional[torc
     return tables
 
 
+# fp32-grade path, 1-D positions: the position bias per linear PIECE of its MLP (csrc/cpb_regions1d.h) - exact, opt-in (cpb_regions=True
+# with 1-D positions; None keeps the per-pair kernels): signed-log offsets, heads // groups in {1, 2}, J <= REGION_MAX_KEYS.
+REGION1D_MAXBP, REGION1D_CELLS, REGION1D_HPG = 32 + 33 * 32, 2048, 2          # csrc/cpb_regions1d.h
+
+
+def region1d_tables_view(tables: torch.Tensor):
+    """Views into a 1-D piece-table buffer (tests / diagnostics; layout: region1d_layout() of csrc/cpb_regions1d.h): breakpoint count,
+    the sorted breakpoints (fp32 and fp64), per piece its ReLU pattern (D1 | D2 << 32) and (a, c) per output [pieces, outputs, 2], the index
+    grid (first piece per cell) and its mapping cell = floor(p * inv + off)."""
+    o = [0]
+
+    def take(nbytes):
+        at = o[0]
+        o[0] += (nbytes + 255) & ~255
+        return at
+    nb, npc, cells = REGION1D_MAXBP, REGION1D_MAXBP + 1, REGION1D_CELLS
+    hdr_o, bp_o, pat_o, coef_o, first_o, bpd_o = take(256), take(nb * 4), take(npc * 8), take(npc * 16), take((cells + 1) * 2), take(nb * 8)
+    hdr = tables[hdr_o:hdr_o + 256].view(torch.int32)
+    n_bp, hpg = int(hdr[0]), int(hdr[1])
+    return {"n_bp": n_bp, "n_pieces": n_bp + 1, "outputs": hpg, "pmax": float(hdr[4:5].view(torch.float32)),
+            "inv": float(hdr[5:6].view(torch.float32)), "off": float(hdr[6:7].view(torch.float32)),
+            "bp": tables[bp_o:bp_o + nb * 4].view(torch.float32)[:n_bp],
+            "bpd": tables[bpd_o:bpd_o + nb * 8].view(torch.float64)[:n_bp],
+            "pat": tables[pat_o:pat_o + npc * 8].view(torch.int64)[:n_bp + 1],
+            "coef": tables[coef_o:coef_o + npc * 16].view(torch.float32).view(npc, REGION1D_HPG, 2)[:n_bp + 1, :hpg],
+            "first": tables[first_o:first_o + (cells + 1) * 2].view(torch.int16)}
+
+
+def cpb_regions1d_build(w1, b1, w2, b2, w3, b3, pmax: float = 0.0, tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The piece tables of the 1-D position-bias MLP with these parameters (index grid over [-pmax, pmax]; 0: the span of the breakpoints),
+    built on the current stream into uint8 scratch owned by the caller."""
+    L = capi.lib()
+    nbytes = L.smml_cpb_regions1d_bytes()
+    if tables is None:
+        tables = torch.empty(nbytes, device=w1.device, dtype=torch.uint8)
+    capi.check(L.smml_cpb_regions1d_build(capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.fptr(_c(w2)), capi.fptr(_c(b2)), capi.fptr(_c(w3)),
+                                          capi.fptr(_c(b3)), int(w3.shape[0]), float(pmax), capi.ptr(tables), nbytes, capi.stream()),
+               "cpb_regions1d_build")
+    return tables
+
+
+def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtype=None, cpb_table=False, log_distance: bool = True):
+    """Why the 1-D piece path cannot take this call (None: it can)."""
+    if vs.shape[-1] != 1:
+        return "the piece path is the 1-D position bias (posdim 1)"
+    if not log_distance:
+        return "raw distances (cpb_log_distance=False)"
+    if compute_dtype is not None:
+        return "the 16-bit compute modes"
+    if cpb_table:
+        return "the table modes"
+    if heads % groups or heads // groups not in (1, 2):
+        return f"heads // groups = {heads // groups if groups else 0} (supported: 1, 2)"
+    if k.shape[1] > REGION_MAX_KEYS:
+        return f"{k.shape[1]} keys (at most {REGION_MAX_KEYS})"
+    if tuple(w2.shape) != (32, 32) or tuple(w3.shape) != (heads // groups, 32):
+        return "a bias MLP other than 1 -> 32 -> 32 -> heads // groups"
+    return None
+
+
+class _DeformAttnRegion1D(torch.autograd.Function):
+    """The fused core with the 1-D position bias per linear piece (include/smml.h, smml_deform_attn_region1d_*)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, pmax):
+        ctx.fork = fork
+        q, k, v, vs, gq = _c(q), _c(k), _c(v), _c(vs), _c(gq)
+        w1, b1, w2, b2, w3, b3 = (_c(t) for t in (w1, b1, w2, b2, w3, b3))
+        B, N, HD = q.shape
+        J = k.shape[1]
+        if HD != heads * 64:
+            raise RuntimeError("the attention kernels are built for dim_head = 64")
+        L = capi.lib()
+        tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
+        out = torch.empty_like(q)
+        lse = torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
+        logits = rid = None
+        if any(ctx.needs_input_grad):
+            nst = L.smml_deform_attn_nst(N)
+            logits = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.float32)
+            rid = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.int16)      # the piece of every pair, per head
+        capi.check(L.smml_deform_attn_region1d_fwd_f32(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.ptr(tables),
+                                                       capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), B, N, J, heads, groups,
+                                                       float(scale), float(dropout_p), int(dropout_seed),
+                                                       *TIMER.events("deform_region1d_fwd", B * heads * N * J), capi.stream(),
+                                                       capi.deform_opts(seed_offset)), "deform_attn_region1d_fwd")
+        ctx.seed_offset = seed_offset
+        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed))
+        ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
+        if DECISION_TAP is not None:       # own key: the ids index the 1-D piece tables (region1d_tables_view), not the 2-D region tables
+            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(),
+                                 "w2": w2.detach(), "b2": b2.detach(), "masks2": None, "region1d_ids": rid, "region1d_tables": tables,
+                                 "B": B, "N": N, "J": J, "heads": heads, "groups": groups, "table_pmax": None, "log_distance": True})
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables = ctx.saved_tensors
+        heads, groups, scale, dropout_p, dropout_seed = ctx.cfg
+        B, N, _ = q.shape
+        J = k.shape[1]
+        L = capi.lib()
+        dout = _c(dout)
+        dlogits = torch.empty_like(logits)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dvs = torch.empty_like(vs)
+        dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3))
+        wsb = L.smml_deform_attn_region1d_bwd_workspace_bytes(B, N, J, heads)
+        ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
+        capi.check(L.smml_deform_attn_region1d_bwd_f32(
+            capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
+            capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), capi.fptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
+            capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3), capi.ptr(ws), wsb,
+            B, N, J, heads, groups, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region1d_bwd", B * heads * N * J), capi.stream(),
+            capi.deform_opts(ctx.seed_offset)), "deform_attn_region1d_bwd")
+        if ctx.fork is not None and ctx.needs_input_grad[0]:
+            ctx.fork.dq = dq.view(B, N, -1)
+        return dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None, None, None, None, None
+
+
 _REGION_STREAMS = {}
 REGION_PREFETCH = __import__("os").environ.get("SMML_REGION_PREFETCH", "1") != "0"
 
@@ -1286,9 +1406,20 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
     table (|error| <= ~1e-3 of the bias range, below the 16-bit operand rounding), the backward differentiates the per-pair MLP itself, recomputing
     layer 2 (parity-grade gradients at the 16-bit mode's tolerances); cpb_table_pmax = half-width of the grid in signed-log units (table_pmax(); None: taken from the data, one host sync);
     cpb_table_grid = (rows, cols) asserts that the queries sit on a regular grid, gq[y * cols + x] = (X[x], Y[y]) - the backward then
-    builds d table on the matrix pipe instead of with LDS atomics."""
+    builds d table on the matrix pipe instead of with LDS atomics.
+    cpb_regions True with 1-D positions: the position bias per linear piece of its MLP (csrc/cpb_regions1d.h; signed-log offsets, the
+    fp32-grade core, heads // groups in {1, 2}; anything else raises), cpb_region_pmax = half-width of its index grid (None: the span of
+    the breakpoints; no host sync either way)."""
     if cpb_table not in (False, True, None, "forward", "full"):
         raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
+    if cpb_regions is not None and bool(cpb_regions) and vs.shape[-1] == 1:
+        # 1-D positions: the piece path only on request (cpb_regions=True), and never a silent fall-back from it
+        why = region1d_unsupported(vs, k, w2, w3, heads=heads, groups=groups, compute_dtype=compute_dtype, cpb_table=cpb_table,
+                                   log_distance=log_distance)
+        if why is not None:
+            raise ValueError(f"cpb_regions=True with 1-D positions: the piece path does not support {why}")
+        return _DeformAttnRegion1D.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
+                                         dropout_seed_offset, fork, cpb_region_pmax)
     if cpb_table and cpb_table_pmax is None:
         cpb_table_pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
     if cpb_table and not log_distance:
