@@ -1299,6 +1299,15 @@ static int check_region(const char* fn, int B, int N, int J, int H) {
   SMML_REQUIRE(J <= RG_MAX_KEYS, "%s: the region kernels take at most %d keys (got %d)", fn, RG_MAX_KEYS, J);
   return SMML_OK;
 }
+static int check_region_workspace(const char* fn, const void* ws, size_t bytes, const RegionBwdPlan& pl, int J) {
+  if (int rc = check_workspace(fn, ws, bytes, pl.total, 256)) return rc;
+  SMML_REQUIRE(pl.wpk >= 1, "%s: too many keys (%d)", fn, J);
+  return SMML_OK;
+}
+// regions whose (a, c) / moments live in LDS: RG_LCAP, or less (opts->region_lds_cap, tests of the global-memory path)
+static int region_lcap(const SmmlDeformOpts* opts) {
+  return (opts && opts->region_lds_cap > 0) ? (opts->region_lds_cap < RG_LCAP ? opts->region_lds_cap : RG_LCAP) : RG_LCAP;
+}
 
 
 // pass 3 of a region backward: d vs per pair, region moments (cpb_region_bwd_kernel<DS>), then the dense pass to the six parameter gradients.

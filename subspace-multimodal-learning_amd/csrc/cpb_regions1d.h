@@ -669,4 +669,29 @@ static int check_region1d(const char* fn, int B, int N, int J, int H, int G) {
   return SMML_OK;
 }
 
+// pass 3 of a piece backward: d vs per pair and piece moments (cpb_region1d_bwd_kernel), then the dense pass to the six parameter gradients.
+// wsb: the call's workspace (bytes), pl: its plan (region_bwd_plan); amax | flag | hist | grad were zeroed and amax filled by the dq pass.
+static int region1d_bias_bwd_launch(const char* fn, const float* dlogits, const unsigned short* region_ids, const float* vs, const float* gq,
+                                    const void* tables, char* wsb, const RegionBwdPlan& pl, int B, int N, int J, int H, int G, int nst, float* dvs,
+                                    float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ev_start, void* ev_stop,
+                                    hipStream_t st) {
+  unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
+  unsigned* flag = amax + 1;                                 // non-finite d score seen (same zeroed 256-byte block)
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(wsb + pl.hist);
+  float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
+  double* part = reinterpret_cast<double*>(wsb + pl.part);
+  const Region1DView rv = region1d_view(tables);
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+  hipLaunchKernelGGL(cpb_region1d_bwd_kernel, dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), 0, st, dlogits, region_ids, vs, gq, rv,
+                     amax, flag, hist, dvs_slab, N, J, H, G, nst, pl.nkb, pl.nkbg, pl.chunks, pl.wpk, pl.tiles_per_chunk, pl.kbits, pl.shift);
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  if (int rc = launch_check(fn, "cpb")) return rc;
+  const size_t n = (size_t)B * G * J;
+  hipLaunchKernelGGL(region1d_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dvs_slab, dvs, B, H, G, J, pl.chunks);
+  hipLaunchKernelGGL(region1d_final1_kernel, dim3(R1_GROUPS), dim3(256), 0, st, region1d_tables(const_cast<void*>(tables)), hist, part);
+  hipLaunchKernelGGL(region1d_final2_kernel, dim3((R1G_N + 255) / 256), dim3(256), 0, st, part, amax, flag, pl.kbits - pl.shift, H / G, dw1, db1, dw2,
+                     db2, dw3, db3);
+  return launch_check(fn, "reduce");
+}
+
 }  // namespace

@@ -27,6 +27,8 @@
 #include "cpb_regions.h"
 #include "cpb_regions1d.h"
 
+extern "C" int smml_deform_attn_nst(int N);
+
 namespace {
 
 
@@ -1149,6 +1151,26 @@ __global__ void drop_mask_kernel(float* __restrict__ mask, unsigned long long to
   mask[i] = (dc.thresh == 0 || ((drop_keep2(dc, row * (unsigned long long)((J + 1) >> 1) + (j >> 1)) >> (j & 1)) & 1u)) ? 1.f : 0.f;
 }
 
+// deform_attn_fwd_kernel<PDX, SAVE> of a launch (PDX = pdx_of(posdim, opts))
+template <int PDX> auto fwd_kernel(bool save) { return save ? deform_attn_fwd_kernel<PDX, true> : deform_attn_fwd_kernel<PDX, false>; }
+
+// backward passes 1 (dS^T, dQ; max |dS| into amax unless it is null) and 2 (dK, dV) of every fp32-grade backward
+int bwd_dq_dkv(const char* fn, const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
+                      const float* logits_t, float* dlogits_t, float* dq, float* dk, float* dv, float* wsf, unsigned* amax, int B, int N, int J,
+                      int H, float scale, DropCfg dc, hipStream_t st) {
+  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
+  const int nst = smml_deform_attn_nst(N);
+  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
+  hipLaunchKernelGGL(deform_attn_bwd_dq_kernel, dim3(qtiles, H, B), dim3(256), 0, st, k, v, out, dout, lse, logits_t, dlogits_t, dq, wsf + wsl.rho,
+                     amax, N, J, H, nst, scale, dc);
+  if (int rc = launch_check(fn, "dq")) return rc;
+  const DkvGrid g = dkv_grid(B, N, J, H);
+  hipLaunchKernelGGL(deform_attn_bwd_dkv_kernel, g.grid, dim3(256), 0, st, q, dout, lse, logits_t, dlogits_t, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H,
+                     nst, g.nkg, g.tpp, g.parts, B, dc);
+  if (int rc = launch_check(fn, "dkv")) return rc;
+  return dkv_reduce_launch(fn, wsf, wsl, dk, dv, B, J, H, g.parts, scale, st);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1192,53 +1214,28 @@ size_t smml_deform_attn_bwd_workspace_bytes(int B, int N, int J, int H) {
   return bwd_workspace(B, N, J, H).total * sizeof(float);
 }
 
-static int check_common(const char* fn, int B, int N, int J, int H, int G, int posdim) {
-  SMML_REQUIRE(B > 0 && N > 0 && J > 0 && H > 0 && G > 0, "%s: non-positive dimension", fn);
-  SMML_REQUIRE(H % G == 0, "%s: heads (%d) must be divisible by offset groups (%d)", fn, H, G);
-  SMML_REQUIRE(H / G <= 2, "%s: at most 2 heads per offset group are supported (got %d)", fn, H / G);
-  SMML_REQUIRE(posdim == 1 || posdim == 2, "%s: posdim must be 1 or 2 (got %d)", fn, posdim);
-  SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
-  return SMML_OK;
-}
-
 int smml_deform_attn_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq,
                              const float* w1, const float* b1, const float* w2, const float* b2,
                              const float* w3, const float* b3, float* out, float* lse, float* logits_t,
                              unsigned short* relu_masks, int B, int N, int J, int H, int G, int posdim, float scale,
                              float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_common("smml_deform_attn_fwd_f32", B, N, J, H, G, posdim);
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_fwd_f32: dropout_p must be in [0, 1)");
-  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  static const char* fn = "smml_deform_attn_fwd_f32";
+  int rc = check_common(fn, B, N, J, H, G, posdim);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && lse,
-               "smml_deform_attn_fwd_f32: null pointer");
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && lse, "%s: null pointer", fn);
+  if ((rc = check_saved(fn, logits_t, relu_masks, "logits_t", "relu_masks"))) return rc;
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B), block(256);
-  const int nst = smml_deform_attn_nst(N);
+  const int pdx = pdx_of(posdim, opts);
+  const bool save = relu_masks != nullptr;
+  const auto kern = pdx == 2 ? fwd_kernel<2>(save) : pdx == 3 ? fwd_kernel<3>(save) : fwd_kernel<1>(save);
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  SMML_REQUIRE((logits_t == nullptr) == (relu_masks == nullptr),
-               "smml_deform_attn_fwd_f32: logits_t and relu_masks are saved together (training) or not at all");
-  if (posdim == 2 && relu_masks)
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<2, true>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
-  else if (posdim == 2)
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<2, false>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
-  else if (pdx_of(posdim, opts) == 3 && relu_masks)         // 1-D, raw offsets (cpb_log_distance = False)
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<3, true>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
-  else if (pdx_of(posdim, opts) == 3)
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<3, false>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
-  else if (relu_masks)
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<1, true>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
-  else
-    hipLaunchKernelGGL((deform_attn_fwd_kernel<1, false>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, logits_t,
-                       relu_masks, N, J, H, G, nst, scale, dc);
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, out, lse, logits_t, relu_masks,
+                     N, J, H, G, smml_deform_attn_nst(N), scale, dc);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn_fwd_f32");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1251,72 +1248,31 @@ int smml_deform_attn_bwd_f32(const float* q, const float* k, const float* v, con
                              float* db3, void* workspace, size_t workspace_bytes, int B, int N, int J, int H,
                              int G, int posdim, float scale, float dropout_p, unsigned long long dropout_seed,
                              void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_common("smml_deform_attn_bwd_f32", B, N, J, H, G, posdim);
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_bwd_f32: dropout_p must be in [0, 1)");
-  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  static const char* fn = "smml_deform_attn_bwd_f32";
+  int rc = check_common(fn, B, N, J, H, G, posdim);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && dout && lse && logits_t &&
                    relu_masks && dlogits_t && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "smml_deform_attn_bwd_f32: null pointer");
-  SMML_REQUIRE(workspace_bytes >= smml_deform_attn_bwd_workspace_bytes(B, N, J, H),
-               "smml_deform_attn_bwd_f32: workspace too small (%zu < %zu)", workspace_bytes,
-               smml_deform_attn_bwd_workspace_bytes(B, N, J, H));
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "smml_deform_attn_bwd_f32: workspace must be 16-byte aligned");
+               "%s: null pointer", fn);
+  if ((rc = check_workspace(fn, workspace, workspace_bytes, smml_deform_attn_bwd_workspace_bytes(B, N, J, H), 16))) return rc;
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   hipStream_t st = (hipStream_t)stream;
-  const int nst = smml_deform_attn_nst(N);
   const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
-  // pass 1: dS^T, dQ
   const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
   float* wsf = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(deform_attn_bwd_dq_kernel, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits_t,
-                     dlogits_t, dq, wsf + wsl.rho, (unsigned*)nullptr, N, J, H, nst, scale, dc);
-  SMML_LAUNCH_CHECK("smml_deform_attn_bwd_f32/dq");
-  // pass 2: dK, dV (query-sliced partial sums, then a fixed-order reduction)
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    hipLaunchKernelGGL(deform_attn_bwd_dkv_kernel, dim3(((nslices + 7) / 8) * 8 * nkg), block, 0, st, q, dout, lse,
-                       logits_t, dlogits_t, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn_bwd_f32/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st,
-                       reinterpret_cast<const float4*>(wsf + wsl.dkp), reinterpret_cast<const float4*>(wsf + wsl.dvp),
-                       reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts, scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn_bwd_f32/dkv_reduce");
-  }
+  if ((rc = bwd_dq_dkv(fn, q, k, v, out, dout, lse, logits_t, dlogits_t, dq, dk, dv, wsf, nullptr, B, N, J, H, scale, dc, st))) return rc;
   // pass 3: position-bias MLP backward
-  {
-    float* slab = (float*)workspace;
-    const size_t lds = ((size_t)CPB2_TAB + WAVES * CPB2_WAVE_LDS + WAVES * CPB_SLAB) * sizeof(float);
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);   // brackets the position-bias backward kernel only
-    if (posdim == 2)
-      hipLaunchKernelGGL(cpb_bwd_kernel<2>, dim3(qtiles, H, B), block, lds, st, dlogits_t, relu_masks, logits_t, lse,
-                         wsf + wsl.rho, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst);
-    else if (pdx_of(posdim, opts) == 3)
-      hipLaunchKernelGGL(cpb_bwd_kernel<3>, dim3(qtiles, H, B), block, lds, st, dlogits_t, relu_masks, logits_t, lse,
-                         wsf + wsl.rho, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst);
-    else
-      hipLaunchKernelGGL(cpb_bwd_kernel<1>, dim3(qtiles, H, B), block, lds, st, dlogits_t, relu_masks, logits_t, lse,
-                         wsf + wsl.rho, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst);
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    SMML_LAUNCH_CHECK("smml_deform_attn_bwd_f32/cpb");
-    const int nwg = qtiles * H * B;
-    {
-      const long long threads = (long long)B * G * J * 4;
-      hipLaunchKernelGGL(dvs_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
-                         reinterpret_cast<const float2*>(wsf + wsl.dvs), dvs, B, G, H, qtiles, J, posdim);
-    }
-    const int nchunks = min(CPB_RED_CHUNKS, nwg), chunk = (nwg + nchunks - 1) / nchunks;
-    hipLaunchKernelGGL(cpb_partial_kernel, dim3((CPB_SLAB + 63) / 64, nchunks), dim3(256), 0, st, slab, nwg, H / G, qtiles,
-                       H, chunk, wsf + wsl.partial);
-    hipLaunchKernelGGL(cpb_final_kernel, dim3((CPB_SLAB + 255) / 256), dim3(256), 0, st, wsf + wsl.partial, nchunks, H / G,
-                       dw1, db1, dw2, db2, dw3, db3, posdim);
-    SMML_LAUNCH_CHECK("smml_deform_attn_bwd_f32/reduce");
-  }
-  return SMML_OK;
+  const int pdx = pdx_of(posdim, opts);
+  const auto kern = pdx == 2 ? cpb_bwd_kernel<2> : pdx == 3 ? cpb_bwd_kernel<3> : cpb_bwd_kernel<1>;
+  const size_t lds = ((size_t)CPB2_TAB + WAVES * CPB2_WAVE_LDS + WAVES * CPB_SLAB) * sizeof(float);
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);   // brackets the position-bias backward kernel only
+  hipLaunchKernelGGL(kern, dim3(qtiles, H, B), dim3(256), lds, st, dlogits_t, relu_masks, logits_t, lse, wsf + wsl.rho, vs, gq, cp, wsf + wsl.slab,
+                     wsf + wsl.dvs, N, J, H, G, smml_deform_attn_nst(N));
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  if ((rc = launch_check(fn, "cpb"))) return rc;
+  return cpb_reduce_launch(fn, wsf, wsl, dvs, dw1, db1, dw2, db2, dw3, db3, B, J, H, G, qtiles, posdim, st);
 }
 
 
@@ -1342,29 +1298,22 @@ int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float*
                                     const float* b3, const void* tables, float* out, float* lse, float* logits_t,
                                     unsigned short* region_ids, int B, int N, int J, int H, float scale, float dropout_p,
                                     unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_region("smml_deform_attn_region_fwd_f32", B, N, J, H);
+  static const char* fn = "smml_deform_attn_region_fwd_f32";
+  int rc = check_region(fn, B, N, J, H);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_region_fwd_f32: dropout_p must be in [0, 1)");
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse,
-               "smml_deform_attn_region_fwd_f32: null pointer");
-  SMML_REQUIRE((logits_t == nullptr) == (region_ids == nullptr),
-               "smml_deform_attn_region_fwd_f32: logits_t and region_ids are saved together (training) or not at all");
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse, "%s: null pointer", fn);
+  if ((rc = check_saved(fn, logits_t, region_ids, "logits_t", "region_ids"))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  const int lcap = (opts && opts->region_lds_cap > 0) ? (opts->region_lds_cap < RG_LCAP ? opts->region_lds_cap : RG_LCAP) : RG_LCAP;
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   const RegionView rv = region_view(const_cast<void*>(tables));
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B), block(256);
-  const int nst = smml_deform_attn_nst(N);
+  const auto kern = region_ids ? deform_region_fwd_kernel<true> : deform_region_fwd_kernel<false>;
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  if (region_ids)
-    hipLaunchKernelGGL(deform_region_fwd_kernel<true>, grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits_t, region_ids, N, J,
-                       H, nst, scale, dc, lcap);
-  else
-    hipLaunchKernelGGL(deform_region_fwd_kernel<false>, grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits_t, region_ids, N, J,
-                       H, nst, scale, dc, lcap);
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits_t, region_ids,
+                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts));
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region_fwd_f32");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1380,52 +1329,25 @@ int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float*
                                     float* dv, float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
                                     void* workspace, size_t workspace_bytes, int B, int N, int J, int H, float scale, float dropout_p,
                                     unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_region("smml_deform_attn_region_bwd_f32", B, N, J, H);
+  static const char* fn = "smml_deform_attn_region_bwd_f32";
+  int rc = check_region(fn, B, N, J, H);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_region_bwd_f32: dropout_p must be in [0, 1)");
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits_t && region_ids &&
                    dlogits_t && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "smml_deform_attn_region_bwd_f32: null pointer");
+               "%s: null pointer", fn);
   const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
-  SMML_REQUIRE(workspace_bytes >= pl.total, "smml_deform_attn_region_bwd_f32: workspace too small (%zu < %zu)", workspace_bytes, pl.total);
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "smml_deform_attn_region_bwd_f32: workspace must be 256-byte aligned");
-  SMML_REQUIRE(pl.wpk >= 1, "smml_deform_attn_region_bwd_f32: too many keys (%d)", J);
+  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  const int lcap = (opts && opts->region_lds_cap > 0) ? (opts->region_lds_cap < RG_LCAP ? opts->region_lds_cap : RG_LCAP) : RG_LCAP;
-  CpbParams cp{w1, b1, w2, b2, w3, b3};
   hipStream_t st = (hipStream_t)stream;
-  const int nst = smml_deform_attn_nst(N);
-  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
-  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
-  float* wsf = reinterpret_cast<float*>(workspace);
   char* wsb = reinterpret_cast<char*>(workspace);
-  unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
-  // the accumulators of this launch: amax | hist | grad are contiguous
-  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);
-  // pass 1: dS^T, dQ, max |dS|
-  hipLaunchKernelGGL(deform_attn_bwd_dq_kernel, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits_t, dlogits_t, dq,
-                     wsf + wsl.rho, amax, N, J, H, nst, scale, dc);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region_bwd_f32/dq");
-  // pass 2: dK, dV
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    hipLaunchKernelGGL(deform_attn_bwd_dkv_kernel, dim3(((nslices + 7) / 8) * 8 * nkg), block, 0, st, q, dout, lse, logits_t, dlogits_t,
-                       wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn_region_bwd_f32/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st, reinterpret_cast<const float4*>(wsf + wsl.dkp),
-                       reinterpret_cast<const float4*>(wsf + wsl.dvp), reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts,
-                       scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn_region_bwd_f32/dkv_reduce");
-  }
-  // pass 3: position bias - d vs per pair, region moments, then the dense pass to the six parameter gradients
-  rc = region_bias_bwd_launch<float>("smml_deform_attn_region_bwd_f32", dlogits_t, region_ids, vs, gq, cp, tables, wsb, pl, B, N, J, H, nst, lcap, dvs,
-                                     dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);      // the accumulators of this launch: amax | hist | grad are contiguous
+  rc = bwd_dq_dkv(fn, q, k, v, out, dout, lse, logits_t, dlogits_t, dq, dk, dv, reinterpret_cast<float*>(workspace),
+                  reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
   if (rc) return rc;
-  return SMML_OK;
+  // pass 3: position bias - d vs per pair, region moments, then the dense pass to the six parameter gradients
+  return region_bias_bwd_launch<float>(fn, dlogits_t, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H,
+                                       smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1450,27 +1372,22 @@ int smml_deform_attn_region1d_fwd_f32(const float* q, const float* k, const floa
                                       float* out, float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G,
                                       float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop,
                                       void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_region1d("smml_deform_attn_region1d_fwd_f32", B, N, J, H, G);
+  static const char* fn = "smml_deform_attn_region1d_fwd_f32";
+  int rc = check_region1d(fn, B, N, J, H, G);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_region1d_fwd_f32: dropout_p must be in [0, 1)");
-  SMML_REQUIRE(q && k && v && vs && gq && tables && out && lse, "smml_deform_attn_region1d_fwd_f32: null pointer");
-  SMML_REQUIRE((logits_t == nullptr) == (region_ids == nullptr),
-               "smml_deform_attn_region1d_fwd_f32: logits_t and region_ids are saved together (training) or not at all");
-  SMML_REQUIRE(!(opts && opts->raw_distance), "smml_deform_attn_region1d_fwd_f32: the piece tables are built for signed-log offsets");
+  SMML_REQUIRE(q && k && v && vs && gq && tables && out && lse, "%s: null pointer", fn);
+  if ((rc = check_saved(fn, logits_t, region_ids, "logits_t", "region_ids"))) return rc;
+  SMML_REQUIRE(!(opts && opts->raw_distance), "%s: the piece tables are built for signed-log offsets", fn);
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   const Region1DView rv = region1d_view(tables);
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B), block(256);
-  const int nst = smml_deform_attn_nst(N);
+  const auto kern = region_ids ? deform_region1d_fwd_kernel<true> : deform_region1d_fwd_kernel<false>;
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  if (region_ids)
-    hipLaunchKernelGGL(deform_region1d_fwd_kernel<true>, grid, block, 0, st, q, k, v, vs, gq, rv, out, lse, logits_t, region_ids, N, J, H,
-                       G, nst, scale, dc);
-  else
-    hipLaunchKernelGGL(deform_region1d_fwd_kernel<false>, grid, block, 0, st, q, k, v, vs, gq, rv, out, lse, logits_t, region_ids, N, J, H,
-                       G, nst, scale, dc);
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, rv, out, lse, logits_t, region_ids,
+                     N, J, H, G, smml_deform_attn_nst(N), scale, dc);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_fwd_f32");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1487,63 +1404,25 @@ int smml_deform_attn_region1d_bwd_f32(const float* q, const float* k, const floa
                                       unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
   static const char* fn = "smml_deform_attn_region1d_bwd_f32";
   int rc = check_region1d(fn, B, N, J, H, G);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p must be in [0, 1)", fn);
   SMML_REQUIRE(q && k && v && vs && gq && tables && out && dout && lse && logits_t && region_ids && dlogits_t && dq && dk && dv && dvs &&
                    dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
                "%s: null pointer", fn);
   SMML_REQUIRE(!(opts && opts->raw_distance), "%s: the piece tables are built for signed-log offsets", fn);
   const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
-  SMML_REQUIRE(workspace_bytes >= pl.total, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, pl.total);
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-  SMML_REQUIRE(pl.wpk >= 1, "%s: too many keys (%d)", fn, J);
+  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   hipStream_t st = (hipStream_t)stream;
-  const int nst = smml_deform_attn_nst(N);
-  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
-  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
-  float* wsf = reinterpret_cast<float*>(workspace);
   char* wsb = reinterpret_cast<char*>(workspace);
-  unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
-  unsigned* flag = amax + 1;                                 // non-finite d score seen (same zeroed 256-byte block)
-  unsigned long long* hist = reinterpret_cast<unsigned long long*>(wsb + pl.hist);
-  float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
-  double* part = reinterpret_cast<double*>(wsb + pl.part);
   (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);      // amax | flag | hist | grad
-  // pass 1: dS^T, dQ, max |dS|; pass 2: dK, dV - the kernels of the 2-D region path, unchanged
-  hipLaunchKernelGGL(deform_attn_bwd_dq_kernel, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits_t, dlogits_t, dq,
-                     wsf + wsl.rho, amax, N, J, H, nst, scale, dc);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dq");
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    hipLaunchKernelGGL(deform_attn_bwd_dkv_kernel, dim3(((nslices + 7) / 8) * 8 * nkg), block, 0, st, q, dout, lse, logits_t, dlogits_t,
-                       wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st, reinterpret_cast<const float4*>(wsf + wsl.dkp),
-                       reinterpret_cast<const float4*>(wsf + wsl.dvp), reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts,
-                       scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/dkv_reduce");
-  }
+  // passes 1 and 2: the kernels of the 2-D region path, unchanged
+  rc = bwd_dq_dkv(fn, q, k, v, out, dout, lse, logits_t, dlogits_t, dq, dk, dv, reinterpret_cast<float*>(workspace),
+                  reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
+  if (rc) return rc;
   // pass 3: position bias - d vs per pair, piece moments, then the dense pass to the six parameter gradients
-  const Region1DView rv = region1d_view(tables);
-  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  hipLaunchKernelGGL(cpb_region1d_bwd_kernel, dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), 0, st, dlogits_t, region_ids, vs,
-                     gq, rv, amax, flag, hist, dvs_slab, N, J, H, G, nst, pl.nkb, pl.nkbg, pl.chunks, pl.wpk, pl.tiles_per_chunk, pl.kbits,
-                     pl.shift);
-  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/cpb");
-  const size_t n = (size_t)B * G * J;
-  hipLaunchKernelGGL(region1d_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dvs_slab, dvs, B, H, G, J, pl.chunks);
-  const Region1DTables rt = region1d_tables(const_cast<void*>(tables));
-  hipLaunchKernelGGL(region1d_final1_kernel, dim3(R1_GROUPS), dim3(256), 0, st, rt, hist, part);
-  hipLaunchKernelGGL(region1d_final2_kernel, dim3((R1G_N + 255) / 256), dim3(256), 0, st, part, amax, flag, pl.kbits - pl.shift, H / G, dw1,
-                     db1, dw2, db2, dw3, db3);
-  SMML_LAUNCH_CHECK("smml_deform_attn_region1d_bwd_f32/reduce");
-  return SMML_OK;
+  return region1d_bias_bwd_launch(fn, dlogits_t, region_ids, vs, gq, tables, wsb, pl, B, N, J, H, G, smml_deform_attn_nst(N), dvs, dw1, db1, dw2,
+                                  db2, dw3, db3, ev_start, ev_stop, st);
 }
 
 }  // extern "C"

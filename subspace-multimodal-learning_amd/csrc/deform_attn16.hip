@@ -21,6 +21,11 @@
 #include "deform16_types.h"
 #include "cpb_regions.h"
 
+extern "C" {
+int smml_deform_attn_nst(int N);
+size_t smml_deform_attn_bwd_workspace_bytes(int B, int N, int J, int H);
+}
+
 // measurement knobs of this file (tests/build_variants.py)
 #ifndef SMML16_FWD_WPS
 #define SMML16_FWD_WPS 2      // waves per SIMD the forward is register-budgeted for
@@ -1337,52 +1342,50 @@ __global__ __launch_bounds__(256) void cpb_mask_table_kernel(CpbParams cp, u16* 
 }
 
 int check16(const char* fn, int B, int N, int J, int H, int G, int posdim, int dtype) {
-  SMML_REQUIRE(B > 0 && N > 0 && J > 0 && H > 0 && G > 0, "%s: non-positive dimension", fn);
-  SMML_REQUIRE(H % G == 0, "%s: heads (%d) must be divisible by offset groups (%d)", fn, H, G);
-  SMML_REQUIRE(H / G <= 2, "%s: at most 2 heads per offset group are supported (got %d)", fn, H / G);
-  SMML_REQUIRE(posdim == 1 || posdim == 2, "%s: posdim must be 1 or 2 (got %d)", fn, posdim);
-  SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
+  if (int rc = check_common(fn, B, N, J, H, G, posdim)) return rc;
   SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
   return SMML_OK;
-}
-
-template <typename T>
-void launch_fwd16(dim3 grid, hipStream_t st, bool save, int posdim, const float* q, const float* k, const float* v, const float* vs,
-                  const float* gq, CpbParams cp, float* out, float* lse, u16* lt, u16* mk, int N, int J, int H, int G, int nst,
-                  float scale, DropCfg dc, const SmmlDeformOpts* opts) {
-  dim3 block(256);
-  if (posdim == 2 && save)
-    hipLaunchKernelGGL((deform16_fwd_kernel<2, true, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
-  else if (posdim == 2)
-    hipLaunchKernelGGL((deform16_fwd_kernel<2, false, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
-  else if (pdx_of(posdim, opts) == 3 && save)              // 1-D, raw offsets (cpb_log_distance = False)
-    hipLaunchKernelGGL((deform16_fwd_kernel<3, true, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
-  else if (pdx_of(posdim, opts) == 3)
-    hipLaunchKernelGGL((deform16_fwd_kernel<3, false, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
-  else if (save)
-    hipLaunchKernelGGL((deform16_fwd_kernel<1, true, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
-  else
-    hipLaunchKernelGGL((deform16_fwd_kernel<1, false, T>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc);
 }
 
 constexpr int TABLE_G2 = 96;      // grid points per axis of the 2-D table (36 KB in LDS: two forward workgroups per CU)
 constexpr int TABLE_G1 = 1024;    // points of the 1-D table
 
-template <typename T>
-void launch_fwd_table(dim3 grid, hipStream_t st, bool save, int posdim, const float* q, const float* k, const float* v, const float* vs,
-                      const float* gq, float* out, float* lse, u16* lt, int N, int J, int H, int G, int nst, float scale, DropCfg dc,
-                      TabCfg tc) {
-  dim3 block(256);
-  const CpbParams cp{};
-  u16* mk = nullptr;
-  if (posdim == 2 && save)
-    hipLaunchKernelGGL((deform16_fwd_kernel<2, true, T, TABLE_G2>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc, tc);
-  else if (posdim == 2)
-    hipLaunchKernelGGL((deform16_fwd_kernel<2, false, T, TABLE_G2>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc, tc);
-  else if (save)
-    hipLaunchKernelGGL((deform16_fwd_kernel<1, true, T, TABLE_G1>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc, tc);
-  else
-    hipLaunchKernelGGL((deform16_fwd_kernel<1, false, T, TABLE_G1>), grid, block, 0, st, q, k, v, vs, gq, cp, out, lse, lt, mk, N, J, H, G, nst, scale, dc, tc);
+// deform16_fwd_kernel<PDX, SAVE, T> of a launch (PDX = pdx_of(posdim, opts)); the table mode (TABLE_G2 / TABLE_G1 points) is signed-log only
+template <typename T> auto fwd16_kernel(int pdx, bool save, bool table) {
+  if (table) {
+    if (pdx == 2) return save ? deform16_fwd_kernel<2, true, T, TABLE_G2> : deform16_fwd_kernel<2, false, T, TABLE_G2>;
+    return save ? deform16_fwd_kernel<1, true, T, TABLE_G1> : deform16_fwd_kernel<1, false, T, TABLE_G1>;
+  }
+  if (pdx == 2) return save ? deform16_fwd_kernel<2, true, T> : deform16_fwd_kernel<2, false, T>;
+  if (pdx == 3) return save ? deform16_fwd_kernel<3, true, T> : deform16_fwd_kernel<3, false, T>;
+  return save ? deform16_fwd_kernel<1, true, T> : deform16_fwd_kernel<1, false, T>;
+}
+
+// cpb16_bwd_kernel of a backward: layer-2 decisions saved by the forward (MSRC 0), else from the mask table (2) or recomputed per pair (1);
+// EXPORT: the decisions are written to opts->export_masks
+auto cpb16_kernel(int pdx, bool saved, bool mask_table, bool exp) {
+  if (saved) return pdx == 2 ? cpb16_bwd_kernel<2> : pdx == 3 ? cpb16_bwd_kernel<3> : cpb16_bwd_kernel<1>;
+  if (pdx == 2 && mask_table) return exp ? cpb16_bwd_kernel<2, 2, true> : cpb16_bwd_kernel<2, 2, false>;
+  if (pdx == 2) return exp ? cpb16_bwd_kernel<2, 1, true> : cpb16_bwd_kernel<2, 1, false>;
+  if (mask_table) return exp ? cpb16_bwd_kernel<1, 2, true> : cpb16_bwd_kernel<1, 2, false>;
+  return exp ? cpb16_bwd_kernel<1, 1, true> : cpb16_bwd_kernel<1, 1, false>;
+}
+
+// backward passes 1 (bf16 d scores, dQ; max |d scores| into amax unless it is null) and 2 (dK, dV) of every 16-bit backward
+int bwd16_dq_dkv(const char* fn, int dtype, const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
+                 const u16* logits16, u16* dlogits16, float* dq, float* dk, float* dv, float* wsf, unsigned* amax, int B, int N, int J, int H,
+                 float scale, DropCfg dc, hipStream_t st) {
+  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
+  const int nst = smml_deform_attn_nst(N);
+  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
+  const auto dq_kernel = dtype == 1 ? deform16_bwd_dq_kernel<_Float16> : deform16_bwd_dq_kernel<__bf16>;
+  hipLaunchKernelGGL(dq_kernel, dim3(qtiles, H, B), dim3(256), 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc, amax);
+  if (int rc = launch_check(fn, "dq")) return rc;
+  const DkvGrid g = dkv_grid(B, N, J, H);
+  hipLaunchKernelGGL(deform16_bwd_dkv_kernel, g.grid, dim3(256), 0, st, q, dout, lse, logits16, dlogits16, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H,
+                     nst, g.nkg, g.tpp, g.parts, B, dc);
+  if (int rc = launch_check(fn, "dkv")) return rc;
+  return dkv_reduce_launch(fn, wsf, wsl, dk, dv, B, J, H, g.parts, scale, st);
 }
 
 TabCfg make_tab(const float* table, int tg, float pmax) {
@@ -1428,30 +1431,28 @@ int check_table(const char* fn, int posdim, int table_g, float pmax, const SmmlD
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int smml_deform_attn_nst(int N);
-size_t smml_deform_attn_bwd_workspace_bytes(int B, int N, int J, int H);
-
 int smml_deform_attn16_fwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
                            const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float* out,
                            float* lse, unsigned short* logits16, unsigned short* relu_masks, int B, int N, int J, int H, int G,
                            int posdim, float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start,
                            void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check16("smml_deform_attn16_fwd", B, N, J, H, G, posdim, dtype);
+  static const char* fn = "smml_deform_attn16_fwd";
+  int rc = check16(fn, B, N, J, H, G, posdim, dtype);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn16_fwd: dropout_p must be in [0, 1)");
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && lse, "smml_deform_attn16_fwd: null pointer");
-  SMML_REQUIRE((logits16 == nullptr) == (relu_masks == nullptr),
-               "smml_deform_attn16_fwd: logits16 and relu_masks are saved together (training) or not at all");
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && lse, "%s: null pointer", fn);
+  if ((rc = check_saved(fn, logits16, relu_masks, "logits16", "relu_masks"))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B);
-  const int nst = smml_deform_attn_nst(N);
+  const int pdx = pdx_of(posdim, opts);
+  const bool save = relu_masks != nullptr;
+  const auto kern = dtype == 1 ? fwd16_kernel<_Float16>(pdx, save, false) : fwd16_kernel<__bf16>(pdx, save, false);
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  if (dtype == 1) launch_fwd16<_Float16>(grid, st, relu_masks != nullptr, posdim, q, k, v, vs, gq, cp, out, lse, logits16, relu_masks, N, J, H, G, nst, scale, dc, opts);
-  else launch_fwd16<__bf16>(grid, st, relu_masks != nullptr, posdim, q, k, v, vs, gq, cp, out, lse, logits16, relu_masks, N, J, H, G, nst, scale, dc, opts);
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, out, lse, logits16, relu_masks, N,
+                     J, H, G, smml_deform_attn_nst(N), scale, dc, TabCfg{});
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn16_fwd");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1462,98 +1463,40 @@ int smml_deform_attn16_bwd(const float* q, const float* k, const float* v, const
                            float* dw2, float* db2, float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B, int N,
                            int J, int H, int G, int posdim, float scale, float dropout_p, unsigned long long dropout_seed,
                            int dtype, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check16("smml_deform_attn16_bwd", B, N, J, H, G, posdim, dtype);
+  static const char* fn = "smml_deform_attn16_bwd";
+  int rc = check16(fn, B, N, J, H, G, posdim, dtype);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn16_bwd: dropout_p must be in [0, 1)");
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && out && dout && lse && logits16 &&
                    dlogits16 && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "smml_deform_attn16_bwd: null pointer");        // relu_masks may be null: layer 2 is then recomputed (table-forward calls)
-  SMML_REQUIRE(workspace_bytes >= smml_deform_attn_bwd_workspace_bytes(B, N, J, H),
-               "smml_deform_attn16_bwd: workspace too small (%zu < %zu)", workspace_bytes,
-               smml_deform_attn_bwd_workspace_bytes(B, N, J, H));
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "smml_deform_attn16_bwd: workspace must be 16-byte aligned");
+               "%s: null pointer", fn);        // relu_masks may be null: layer 2 is then recomputed (table-forward calls)
+  if ((rc = check_workspace(fn, workspace, workspace_bytes, smml_deform_attn_bwd_workspace_bytes(B, N, J, H), 16))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   hipStream_t st = (hipStream_t)stream;
-  const int nst = smml_deform_attn_nst(N);
   const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
   const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
   float* wsf = reinterpret_cast<float*>(workspace);
-  // pass 1: d scores (bf16), dQ
-  if (dtype == 1)
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<_Float16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc);
-  else
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<__bf16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc);
-  SMML_LAUNCH_CHECK("smml_deform_attn16_bwd/dq");
-  // pass 2: dK, dV (query-sliced partial sums, then a fixed-order reduction)
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    const dim3 gk(((nslices + 7) / 8) * 8 * nkg);
-    hipLaunchKernelGGL(deform16_bwd_dkv_kernel, gk, block, 0, st, q, dout, lse, logits16, dlogits16, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_bwd/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st,
-                       reinterpret_cast<const float4*>(wsf + wsl.dkp), reinterpret_cast<const float4*>(wsf + wsl.dvp),
-                       reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts, scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_bwd/dkv_reduce");
-  }
+  if ((rc = bwd16_dq_dkv(fn, dtype, q, k, v, out, dout, lse, logits16, dlogits16, dq, dk, dv, wsf, nullptr, B, N, J, H, scale, dc, st))) return rc;
   // pass 3: position-bias MLP backward
-  {
-    float* slab = wsf;
-    const size_t lds = ((size_t)CPB2_TAB + WAVES * CPB2_WAVE_LDS + WAVES * CPB_SLAB) * sizeof(float);
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);   // brackets the position-bias backward kernel only
-    u16* mko = opts ? opts->export_masks : nullptr;
-    const dim3 gc(qtiles, H, B);
-    if (relu_masks) {
-      if (posdim == 2)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<2>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-      else if (pdx_of(posdim, opts) == 3)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<3>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-      else
-        hipLaunchKernelGGL((cpb16_bwd_kernel<1>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-    } else if (opts && opts->mask_table) {          // decisions from the mask table
-      const int cells = posdim == 2 ? 1024 : 16384;
-      MaskTab mt;
-      mt.tab = opts->mask_table;
-      mt.invh = (float)((double)cells / (2.0 * (double)opts->mask_table_pmax));
-      mt.off = 0.5f * (float)cells;
-      mt.imax = (float)cells - 0.5f;
-      if (posdim == 2 && mko)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<2, 2, true>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko, mt);
-      else if (posdim == 2)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<2, 2, false>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko, mt);
-      else if (mko)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<1, 2, true>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko, mt);
-      else
-        hipLaunchKernelGGL((cpb16_bwd_kernel<1, 2, false>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko, mt);
-    } else if (mko) {                   // layer 2 recomputed per pair
-      if (posdim == 2)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<2, 1, true>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-      else
-        hipLaunchKernelGGL((cpb16_bwd_kernel<1, 1, true>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-    } else {
-      if (posdim == 2)
-        hipLaunchKernelGGL((cpb16_bwd_kernel<2, 1, false>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-      else
-        hipLaunchKernelGGL((cpb16_bwd_kernel<1, 1, false>), gc, block, lds, st, dlogits16, relu_masks, vs, gq, cp, slab, wsf + wsl.dvs, N, J, H, G, nst, mko);
-    }
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_bwd/cpb");
-    const int nwg = qtiles * H * B;
-    {
-      const long long threads = (long long)B * G * J * 4;
-      hipLaunchKernelGGL(dvs_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
-                         reinterpret_cast<const float2*>(wsf + wsl.dvs), dvs, B, G, H, qtiles, J, posdim);
-    }
-    const int nchunks = min(CPB_RED_CHUNKS, nwg), chunk = (nwg + nchunks - 1) / nchunks;
-    hipLaunchKernelGGL(cpb_partial_kernel, dim3((CPB_SLAB + 63) / 64, nchunks), dim3(256), 0, st, slab, nwg, H / G, qtiles, H, chunk, wsf + wsl.partial);
-    hipLaunchKernelGGL(cpb_final_kernel, dim3((CPB_SLAB + 255) / 256), dim3(256), 0, st, wsf + wsl.partial, nchunks, H / G, dw1, db1, dw2, db2, dw3, db3, posdim);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_bwd/reduce");
+  u16* mko = opts ? opts->export_masks : nullptr;
+  const bool mask_table = !relu_masks && opts && opts->mask_table;
+  MaskTab mt{};
+  if (mask_table) {
+    const int cells = posdim == 2 ? 1024 : 16384;
+    mt.tab = opts->mask_table;
+    mt.invh = (float)((double)cells / (2.0 * (double)opts->mask_table_pmax));
+    mt.off = 0.5f * (float)cells;
+    mt.imax = (float)cells - 0.5f;
   }
-  return SMML_OK;
+  const auto kern = cpb16_kernel(pdx_of(posdim, opts), relu_masks != nullptr, mask_table, mko != nullptr);
+  const size_t lds = ((size_t)CPB2_TAB + WAVES * CPB2_WAVE_LDS + WAVES * CPB_SLAB) * sizeof(float);
+  if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);   // brackets the position-bias backward kernel only
+  hipLaunchKernelGGL(kern, dim3(qtiles, H, B), dim3(256), lds, st, dlogits16, relu_masks, vs, gq, cp, wsf + wsl.slab, wsf + wsl.dvs, N, J, H, G,
+                     smml_deform_attn_nst(N), mko, mt);
+  if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+  if ((rc = launch_check(fn, "cpb"))) return rc;
+  return cpb_reduce_launch(fn, wsf, wsl, dvs, dw1, db1, dw2, db2, dw3, db3, B, J, H, G, qtiles, posdim, st);
 }
 
 // ---- position bias per linear region (cpb_regions.h) in the 16-bit compute modes: the bias is the fp32 lookup of the fp32-grade path, the
@@ -1563,34 +1506,24 @@ int smml_deform_attn16_region_fwd(const float* q, const float* k, const float* v
                                   float* out, float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H,
                                   float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop,
                                   void* stream, const SmmlDeformOpts* opts) {
-  int rc = check_region("smml_deform_attn16_region_fwd", B, N, J, H);
+  static const char* fn = "smml_deform_attn16_region_fwd";
+  int rc = check_region(fn, B, N, J, H);
   if (rc) return rc;
-  SMML_REQUIRE(dtype == 0 || dtype == 1, "smml_deform_attn16_region_fwd: dtype must be 0 (bf16) or 1 (fp16), got %d", dtype);
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn16_region_fwd: dropout_p must be in [0, 1)");
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse, "smml_deform_attn16_region_fwd: null pointer");
-  SMML_REQUIRE((logits16 == nullptr) == (region_ids == nullptr),
-               "smml_deform_attn16_region_fwd: logits16 and region_ids are saved together (training) or not at all");
+  SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
+  if ((rc = check_dropout(fn, dropout_p))) return rc;
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse, "%s: null pointer", fn);
+  if ((rc = check_saved(fn, logits16, region_ids, "logits16", "region_ids"))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  const int lcap = (opts && opts->region_lds_cap > 0) ? (opts->region_lds_cap < RG_LCAP ? opts->region_lds_cap : RG_LCAP) : RG_LCAP;
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   const RegionView rv = region_view(const_cast<void*>(tables));
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B), block(256);
-  const int nst = smml_deform_attn_nst(N);
+  const auto kern = dtype == 1 ? (region_ids ? deform_region_fwd_kernel<true, _Float16> : deform_region_fwd_kernel<false, _Float16>)
+                               : (region_ids ? deform_region_fwd_kernel<true, __bf16> : deform_region_fwd_kernel<false, __bf16>);
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  if (dtype == 1) {
-    if (region_ids)
-      hipLaunchKernelGGL((deform_region_fwd_kernel<true, _Float16>), grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids, N, J, H, nst, scale, dc, lcap);
-    else
-      hipLaunchKernelGGL((deform_region_fwd_kernel<false, _Float16>), grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids, N, J, H, nst, scale, dc, lcap);
-  } else {
-    if (region_ids)
-      hipLaunchKernelGGL((deform_region_fwd_kernel<true, __bf16>), grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids, N, J, H, nst, scale, dc, lcap);
-    else
-      hipLaunchKernelGGL((deform_region_fwd_kernel<false, __bf16>), grid, block, 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids, N, J, H, nst, scale, dc, lcap);
-  }
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids,
+                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts));
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn16_region_fwd");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1603,52 +1536,26 @@ int smml_deform_attn16_region_bwd(const float* q, const float* k, const float* v
                                   size_t workspace_bytes, int B, int N, int J, int H, float scale, float dropout_p,
                                   unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
                                   const SmmlDeformOpts* opts) {
-  int rc = check_region("smml_deform_attn16_region_bwd", B, N, J, H);
+  static const char* fn = "smml_deform_attn16_region_bwd";
+  int rc = check_region(fn, B, N, J, H);
   if (rc) return rc;
-  SMML_REQUIRE(dtype == 0 || dtype == 1, "smml_deform_attn16_region_bwd: dtype must be 0 (bf16) or 1 (fp16), got %d", dtype);
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn16_region_bwd: dropout_p must be in [0, 1)");
+  SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
+  if ((rc = check_dropout(fn, dropout_p))) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits16 && region_ids &&
                    dlogits16 && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "smml_deform_attn16_region_bwd: null pointer");
+               "%s: null pointer", fn);
   const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
-  SMML_REQUIRE(workspace_bytes >= pl.total, "smml_deform_attn16_region_bwd: workspace too small (%zu < %zu)", workspace_bytes, pl.total);
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "smml_deform_attn16_region_bwd: workspace must be 256-byte aligned");
-  SMML_REQUIRE(pl.wpk >= 1, "smml_deform_attn16_region_bwd: too many keys (%d)", J);
+  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  const int lcap = (opts && opts->region_lds_cap > 0) ? (opts->region_lds_cap < RG_LCAP ? opts->region_lds_cap : RG_LCAP) : RG_LCAP;
-  CpbParams cp{w1, b1, w2, b2, w3, b3};
   hipStream_t st = (hipStream_t)stream;
-  const int nst = smml_deform_attn_nst(N);
-  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
-  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
-  float* wsf = reinterpret_cast<float*>(workspace);
   char* wsb = reinterpret_cast<char*>(workspace);
-  unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
   (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);        // amax | hist | grad are contiguous
-  // pass 1: d scores (bf16), dQ, max |d scores|
-  if (dtype == 1)
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<_Float16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc, amax);
-  else
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<__bf16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc, amax);
-  SMML_LAUNCH_CHECK("smml_deform_attn16_region_bwd/dq");
-  // pass 2: dK, dV (query-sliced partial sums, then a fixed-order reduction)
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    const dim3 gk(((nslices + 7) / 8) * 8 * nkg);
-    hipLaunchKernelGGL(deform16_bwd_dkv_kernel, gk, block, 0, st, q, dout, lse, logits16, dlogits16, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_region_bwd/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st,
-                       reinterpret_cast<const float4*>(wsf + wsl.dkp), reinterpret_cast<const float4*>(wsf + wsl.dvp),
-                       reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts, scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn16_region_bwd/dkv_reduce");
-  }
+  rc = bwd16_dq_dkv(fn, dtype, q, k, v, out, dout, lse, logits16, dlogits16, dq, dk, dv, reinterpret_cast<float*>(workspace),
+                    reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
+  if (rc) return rc;
   // pass 3: position bias per region on the bf16 d scores
-  return region_bias_bwd_launch<u16>("smml_deform_attn16_region_bwd", dlogits16, region_ids, vs, gq, cp, tables, wsb, pl, B, N, J, H, nst, lcap, dvs,
-                                     dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+  return region_bias_bwd_launch<u16>(fn, dlogits16, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H,
+                                     smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
 }
 
 // mask table of the table-forward backward (include/smml.h): cells per axis, and the kernel that fills one
@@ -1680,22 +1587,21 @@ int smml_deform_attn_table_fwd(const float* q, const float* k, const float* v, c
                                float* out, float* lse, unsigned short* logits16, int B, int N, int J, int H, int G, int posdim,
                                int table_g, float table_pmax, float scale, float dropout_p, unsigned long long dropout_seed, int dtype,
                                void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check16("smml_deform_attn_table_fwd", B, N, J, H, G, posdim, dtype);
+  static const char* fn = "smml_deform_attn_table_fwd";
+  int rc = check16(fn, B, N, J, H, G, posdim, dtype);
+  if (!rc) rc = check_table(fn, posdim, table_g, table_pmax, opts);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  rc = check_table("smml_deform_attn_table_fwd", posdim, table_g, table_pmax, opts);
-  if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_table_fwd: dropout_p must be in [0, 1)");
-  SMML_REQUIRE(q && k && v && vs && gq && table && out && lse, "smml_deform_attn_table_fwd: null pointer");
+  SMML_REQUIRE(q && k && v && vs && gq && table && out && lse, "%s: null pointer", fn);
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  const TabCfg tc = make_tab(table, table_g, table_pmax);
-  dim3 grid((N + QT * WAVES - 1) / (QT * WAVES), H, B);
-  const int nst = smml_deform_attn_nst(N);
+  const bool save = logits16 != nullptr;
+  const auto kern = dtype == 1 ? fwd16_kernel<_Float16>(posdim, save, true) : fwd16_kernel<__bf16>(posdim, save, true);
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  if (dtype == 1) launch_fwd_table<_Float16>(grid, st, logits16 != nullptr, posdim, q, k, v, vs, gq, out, lse, logits16, N, J, H, G, nst, scale, dc, tc);
-  else launch_fwd_table<__bf16>(grid, st, logits16 != nullptr, posdim, q, k, v, vs, gq, out, lse, logits16, N, J, H, G, nst, scale, dc, tc);
+  hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, CpbParams{}, out, lse, logits16,
+                     (u16*)nullptr, N, J, H, G, smml_deform_attn_nst(N), scale, dc, make_tab(table, table_g, table_pmax));
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-  SMML_LAUNCH_CHECK("smml_deform_attn_table_fwd");
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
 
@@ -1705,48 +1611,24 @@ int smml_deform_attn_table_bwd(const float* q, const float* k, const float* v, c
                                size_t workspace_bytes, int B, int N, int J, int H, int G, int posdim, int table_g, float table_pmax,
                                int grid_h, int grid_w, float scale, float dropout_p, unsigned long long dropout_seed, int dtype,
                                void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = check16("smml_deform_attn_table_bwd", B, N, J, H, G, posdim, dtype);
+  static const char* fn = "smml_deform_attn_table_bwd";
+  int rc = check16(fn, B, N, J, H, G, posdim, dtype);
+  if (!rc) rc = check_table(fn, posdim, table_g, table_pmax, opts);
+  if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
-  rc = check_table("smml_deform_attn_table_bwd", posdim, table_g, table_pmax, opts);
-  if (rc) return rc;
-  SMML_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "smml_deform_attn_table_bwd: dropout_p must be in [0, 1)");
   SMML_REQUIRE(q && k && v && vs && gq && table && out && dout && lse && logits16 && dlogits16 && dq && dk && dv && dvs && dtable && workspace,
-               "smml_deform_attn_table_bwd: null pointer");
-  const size_t need = smml_deform_attn_table_bwd_workspace_bytes(B, N, J, H, posdim);
-  SMML_REQUIRE(workspace_bytes >= need, "smml_deform_attn_table_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
-  SMML_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "smml_deform_attn_table_bwd: workspace must be 16-byte aligned");
+               "%s: null pointer", fn);
+  if ((rc = check_workspace(fn, workspace, workspace_bytes, smml_deform_attn_table_bwd_workspace_bytes(B, N, J, H, posdim), 16))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   const TabCfg tc = make_tab(table, table_g, table_pmax);
   hipStream_t st = (hipStream_t)stream;
   const int nst = smml_deform_attn_nst(N);
-  const int qtiles = (N + QT * WAVES - 1) / (QT * WAVES);
-  dim3 block(256);
-  const BwdWorkspace wsl = bwd_workspace(B, N, J, H);
   const int cells = posdim == 2 ? TABLE_G2 * TABLE_G2 : TABLE_G1;
   const TableWorkspace tw = table_workspace(B, N, J, H, cells);
   float* wsf = reinterpret_cast<float*>(workspace);
   const int o = H / G;
   (void)hipMemsetAsync(dtable, 0, (size_t)o * cells * sizeof(float), st);
-  // pass 1: d scores (bf16), dQ
-  if (dtype == 1)
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<_Float16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc);
-  else
-    hipLaunchKernelGGL(deform16_bwd_dq_kernel<__bf16>, dim3(qtiles, H, B), block, 0, st, k, v, out, dout, lse, logits16, dlogits16, dq, N, J, H, nst, scale, dc);
-  SMML_LAUNCH_CHECK("smml_deform_attn_table_bwd/dq");
-  // pass 2: dK, dV
-  {
-    const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
-    const int parts = dkv_parts(B, N, J, H), tpp = (nqt + parts - 1) / parts;
-    const int nslices = parts * H * B;
-    const dim3 gk(((nslices + 7) / 8) * 8 * nkg);
-    hipLaunchKernelGGL(deform16_bwd_dkv_kernel, gk, block, 0, st, q, dout, lse, logits16, dlogits16, wsf + wsl.dkp, wsf + wsl.dvp, N, J, H, nst, nkg, tpp, parts, B, dc);
-    SMML_LAUNCH_CHECK("smml_deform_attn_table_bwd/dkv");
-    const size_t n4 = (size_t)B * J * H * DH / 4;
-    hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), block, 0, st,
-                       reinterpret_cast<const float4*>(wsf + wsl.dkp), reinterpret_cast<const float4*>(wsf + wsl.dvp),
-                       reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts, scale);
-    SMML_LAUNCH_CHECK("smml_deform_attn_table_bwd/dkv_reduce");
-  }
+  if ((rc = bwd16_dq_dkv(fn, dtype, q, k, v, out, dout, lse, logits16, dlogits16, dq, dk, dv, wsf, nullptr, B, N, J, H, scale, dc, st))) return rc;
   // pass 3: d table (histogram of d bias over the table cells) and d vs
   {
     const int S = table_slices(B, N, J, H), nkb = (J + 63) / 64, ntq = (N + 31) / 32, tps = (ntq + S - 1) / S;

@@ -511,4 +511,74 @@ DropCfg make_drop(float p, unsigned long long seed, const SmmlDeformOpts* opts) 
   return dc;
 }
 
+// ---- host checks shared by the entry points (every message names the entry point fn)
+// dimensions of a per-pair (MLP) entry point
+int check_common(const char* fn, int B, int N, int J, int H, int G, int posdim) {
+  SMML_REQUIRE(B > 0 && N > 0 && J > 0 && H > 0 && G > 0, "%s: non-positive dimension", fn);
+  SMML_REQUIRE(H % G == 0, "%s: heads (%d) must be divisible by offset groups (%d)", fn, H, G);
+  SMML_REQUIRE(H / G <= 2, "%s: at most 2 heads per offset group are supported (got %d)", fn, H / G);
+  SMML_REQUIRE(posdim == 1 || posdim == 2, "%s: posdim must be 1 or 2 (got %d)", fn, posdim);
+  SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
+  return SMML_OK;
+}
+int check_dropout(const char* fn, float p) {
+  SMML_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout_p must be in [0, 1)", fn);
+  return SMML_OK;
+}
+// the scores and their decisions / region ids are saved together (training) or not at all
+int check_saved(const char* fn, const void* scores, const void* ids, const char* scores_name, const char* ids_name) {
+  SMML_REQUIRE((scores == nullptr) == (ids == nullptr), "%s: %s and %s are saved together (training) or not at all", fn, scores_name, ids_name);
+  return SMML_OK;
+}
+int check_workspace(const char* fn, const void* ws, size_t bytes, size_t need, size_t align) {
+  SMML_REQUIRE(bytes >= need, "%s: workspace too small (%zu < %zu)", fn, bytes, need);
+  SMML_REQUIRE((reinterpret_cast<size_t>(ws) & (align - 1)) == 0, "%s: workspace must be %zu-byte aligned", fn, align);
+  return SMML_OK;
+}
+// SMML_LAUNCH_CHECK of one pass of an entry point: "<fn>/<pass>: launch failed: ..."
+int launch_check(const char* fn, const char* pass) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return SMML_OK;
+  smml_set_error("%s/%s: launch failed: %s", fn, pass, hipGetErrorString(e));
+  return SMML_ERR_HIP;
+}
+
+// backward pass 2 (dK, dV): query-sliced partial sums into the dkp / dvp slabs of the workspace, then a fixed-order reduction
+struct DkvGrid {
+  int nkg, parts, tpp;   // key groups, query slices, 32-query tiles per slice
+  dim3 grid;
+};
+DkvGrid dkv_grid(int B, int N, int J, int H) {
+  DkvGrid g;
+  g.nkg = (J + DKV_KEYS - 1) / DKV_KEYS;
+  g.parts = dkv_parts(B, N, J, H);
+  g.tpp = ((N + QT - 1) / QT + g.parts - 1) / g.parts;
+  const int nslices = g.parts * H * B;
+  g.grid = dim3(((nslices + 7) / 8) * 8 * g.nkg);
+  return g;
+}
+int dkv_reduce_launch(const char* fn, const float* wsf, const BwdWorkspace& wsl, float* dk, float* dv, int B, int J, int H, int parts,
+                      float scale, hipStream_t st) {
+  const size_t n4 = (size_t)B * J * H * DH / 4;
+  hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(wsf + wsl.dkp),
+                     reinterpret_cast<const float4*>(wsf + wsl.dvp), reinterpret_cast<float4*>(dk), reinterpret_cast<float4*>(dv), n4, parts, scale);
+  return launch_check(fn, "dkv_reduce");
+}
+
+// tail of the per-pair position-bias backward (after cpb_bwd_kernel / cpb16_bwd_kernel): the d vs rows into d vs, the per-workgroup
+// slabs into the six parameter gradients
+int cpb_reduce_launch(const char* fn, float* wsf, const BwdWorkspace& wsl, float* dvs, float* dw1, float* db1, float* dw2, float* db2,
+                      float* dw3, float* db3, int B, int J, int H, int G, int qtiles, int posdim, hipStream_t st) {
+  const int nwg = qtiles * H * B;
+  const long long threads = (long long)B * G * J * 4;
+  hipLaunchKernelGGL(dvs_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(wsf + wsl.dvs),
+                     dvs, B, G, H, qtiles, J, posdim);
+  const int nchunks = min(CPB_RED_CHUNKS, nwg), chunk = (nwg + nchunks - 1) / nchunks;
+  hipLaunchKernelGGL(cpb_partial_kernel, dim3((CPB_SLAB + 63) / 64, nchunks), dim3(256), 0, st, wsf + wsl.slab, nwg, H / G, qtiles, H, chunk,
+                     wsf + wsl.partial);
+  hipLaunchKernelGGL(cpb_final_kernel, dim3((CPB_SLAB + 255) / 256), dim3(256), 0, st, wsf + wsl.partial, nchunks, H / G, dw1, db1, dw2, db2, dw3,
+                     db3, posdim);
+  return launch_check(fn, "reduce");
+}
+
 }  // namespace

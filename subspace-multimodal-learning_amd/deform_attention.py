@@ -158,15 +158,23 @@ class DeformCrossAttention2D(nn.Module):
         vsb = max(abs(2.0 * (max(th, tw) - 1 + self.offset_scale) / lo_k - 1.0), 1.0 + 2.0 * self.offset_scale / lo_k)
         return Fh.table_pmax(gqb, vsb)
 
-    def _regions_apply(self) -> bool:
-        return (Fh.CPB_REGIONS and not self.cpb_table and not self.consistent_grid_norm and self.heads == self.offset_groups
-                and self.rel_pos_bias.mlp[0][0].weight.is_cuda)          # fp32-grade core and the 16-bit compute modes alike
+    def _regions_apply(self, n_tokens: int) -> bool:
+        """Whether forward_tokens on a bag of n_tokens takes the region path with the pmax of _region_pmax (functional.deform_path)."""
+        if self.consistent_grid_norm or not self.rel_pos_bias.mlp[0][0].weight.is_cuda:
+            return False
+        Hh, Ww = self._grid(n_tokens)
+        L = Fh.capi.lib()
+        keys = (L.smml_offsets_out_len(Hh, self.offset_kernel_size, self.downsample_factor)
+                * L.smml_offsets_out_len(Ww, self.offset_kernel_size, self.downsample_factor))
+        w = self.rel_pos_bias.tensors()
+        return Fh.deform_path(posdim=2, heads=self.heads, groups=self.offset_groups, keys=keys, w2_shape=w[2].shape, w3_shape=w[4].shape,
+                              compute_dtype=self.compute_dtype, cpb_table=self.cpb_table, region_pmax_given=True) == "region"
 
     def prefetch_regions(self, n_tokens: int) -> None:
         """Starts the build of the position bias's region tables on a side stream (functional.RegionPrefetch); the next forward_tokens on
         a bag of n_tokens joins it.  Optional: without it the tables are built in front of the attention launch."""
         self._prefetch = None
-        if not (self._regions_apply() and Fh.REGION_PREFETCH):
+        if not (Fh.REGION_PREFETCH and self._regions_apply(n_tokens)):
             return
         Hh, Ww = self._grid(n_tokens)
         self._prefetch = Fh.RegionPrefetch(*self.rel_pos_bias.tensors(), self._region_pmax(Hh, Ww))

@@ -874,28 +874,31 @@ REGION_GRID, REGION_SUB, REGION_SUBCAP, REGION_EDGES, REGION_RCAP = 1024, 8, 163
 REGION_CODE_SUB0, REGION_CODE_EDGE0 = 4096, 4096 + 16384
 
 
+def _blocks(tables: torch.Tensor, *sizes):
+    """Consecutive blocks of a table buffer, each starting on a 256-byte boundary (the take() of region_layout() / region1d_layout())."""
+    out, o = [], 0
+    for n in sizes:
+        out.append(tables[o:o + n])
+        o += (n + 255) & ~255
+    return out
+
+
 def region_tables_view(tables: torch.Tensor):
     """Views into a region-table buffer (tests / diagnostics; layout: region_layout() of csrc/cpb_regions.h): header counters,
     (a0, a1, c) per region, ReLU patterns (D1 | D2 << 32), 16-bit codes of the cells and sub-cells, single-kink records by slot."""
-    o = [0]
-
-    def take(nbytes):
-        at = o[0]
-        o[0] += (nbytes + 255) & ~255
-        return at
     G, SUB = REGION_GRID, REGION_SUB
-    hdr_o, reg_o, pat_o = take(256), take(REGION_RCAP * 16), take(REGION_RCAP * 8)
-    t0_o, t1_o, edge_o = take(G * G * 2), take(REGION_SUBCAP * SUB * SUB * 2), take(REGION_EDGES * 16)
-    hdr = tables[hdr_o:hdr_o + 256].view(torch.int32)
+    hdr, reg, pat, t0, t1, edge = _blocks(tables, 256, REGION_RCAP * 16, REGION_RCAP * 8, G * G * 2, REGION_SUBCAP * SUB * SUB * 2,
+                                          REGION_EDGES * 16)
+    hdr = hdr.view(torch.int32)
     n_sub, n_edge, n_regions = int(hdr[0]), int(hdr[1]), int(hdr[3])
     return {"n_sub": n_sub, "n_edge": n_edge, "n_cand": int(hdr[2]), "n_regions": n_regions, "n_keys": int(hdr[4]), "overflow": int(hdr[5]),
             "n_cand1": int(hdr[6]), "pmax": float(hdr[8:9].view(torch.float32)), "cs": float(hdr[9:10].view(torch.float32)),
             "co": float(hdr[10:11].view(torch.float32)),
-            "reg": tables[reg_o:reg_o + REGION_RCAP * 16].view(torch.float32).view(REGION_RCAP, 4)[:n_regions],
-            "pat": tables[pat_o:pat_o + REGION_RCAP * 8].view(torch.int64)[:n_regions],
-            "t0": tables[t0_o:t0_o + G * G * 2].view(torch.int16).view(G, G),
-            "t1": tables[t1_o:t1_o + REGION_SUBCAP * SUB * SUB * 2].view(torch.int16).view(REGION_SUBCAP, SUB * SUB)[:max(min(n_sub, REGION_SUBCAP), 1)],
-            "edge": tables[edge_o:edge_o + REGION_EDGES * 16].view(torch.float32).view(REGION_EDGES, 4)}
+            "reg": reg.view(torch.float32).view(REGION_RCAP, 4)[:n_regions],
+            "pat": pat.view(torch.int64)[:n_regions],
+            "t0": t0.view(torch.int16).view(G, G),
+            "t1": t1.view(torch.int16).view(REGION_SUBCAP, SUB * SUB)[:max(min(n_sub, REGION_SUBCAP), 1)],
+            "edge": edge.view(torch.float32).view(REGION_EDGES, 4)}
 
 
 def region_patterns(region_ids: torch.Tensor, tables: torch.Tensor):
@@ -930,23 +933,17 @@ def region1d_tables_view(tables: torch.Tensor):
     """Views into a 1-D piece-table buffer (tests / diagnostics; layout: region1d_layout() of csrc/cpb_regions1d.h): breakpoint count,
     the sorted breakpoints (fp32 and fp64), per piece its ReLU pattern (D1 | D2 << 32) and (a, c) per output [pieces, outputs, 2], the index
     grid (first piece per cell) and its mapping cell = floor(p * inv + off)."""
-    o = [0]
-
-    def take(nbytes):
-        at = o[0]
-        o[0] += (nbytes + 255) & ~255
-        return at
     nb, npc, cells = REGION1D_MAXBP, REGION1D_MAXBP + 1, REGION1D_CELLS
-    hdr_o, bp_o, pat_o, coef_o, first_o, bpd_o = take(256), take(nb * 4), take(npc * 8), take(npc * 16), take((cells + 1) * 2), take(nb * 8)
-    hdr = tables[hdr_o:hdr_o + 256].view(torch.int32)
+    hdr, bp, pat, coef, first, bpd = _blocks(tables, 256, nb * 4, npc * 8, npc * 16, (cells + 1) * 2, nb * 8)
+    hdr = hdr.view(torch.int32)
     n_bp, hpg = int(hdr[0]), int(hdr[1])
     return {"n_bp": n_bp, "n_pieces": n_bp + 1, "outputs": hpg, "pmax": float(hdr[4:5].view(torch.float32)),
             "inv": float(hdr[5:6].view(torch.float32)), "off": float(hdr[6:7].view(torch.float32)),
-            "bp": tables[bp_o:bp_o + nb * 4].view(torch.float32)[:n_bp],
-            "bpd": tables[bpd_o:bpd_o + nb * 8].view(torch.float64)[:n_bp],
-            "pat": tables[pat_o:pat_o + npc * 8].view(torch.int64)[:n_bp + 1],
-            "coef": tables[coef_o:coef_o + npc * 16].view(torch.float32).view(npc, REGION1D_HPG, 2)[:n_bp + 1, :hpg],
-            "first": tables[first_o:first_o + (cells + 1) * 2].view(torch.int16)}
+            "bp": bp.view(torch.float32)[:n_bp],
+            "bpd": bpd.view(torch.float64)[:n_bp],
+            "pat": pat.view(torch.int64)[:n_bp + 1],
+            "coef": coef.view(torch.float32).view(npc, REGION1D_HPG, 2)[:n_bp + 1, :hpg],
+            "first": first.view(torch.int16)}
 
 
 def cpb_regions1d_build(w1, b1, w2, b2, w3, b3, pmax: float = 0.0, tables: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -962,9 +959,8 @@ def cpb_regions1d_build(w1, b1, w2, b2, w3, b3, pmax: float = 0.0, tables: Optio
     return tables
 
 
-def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtype=None, cpb_table=False, log_distance: bool = True):
-    """Why the 1-D piece path cannot take this call (None: it can)."""
-    if vs.shape[-1] != 1:
+def _region1d_why(posdim: int, keys: int, w2_shape, w3_shape, heads: int, groups: int, compute_dtype, cpb_table, log_distance: bool):
+    if posdim != 1:
         return "the piece path is the 1-D position bias (posdim 1)"
     if not log_distance:
         return "raw distances (cpb_log_distance=False)"
@@ -974,71 +970,168 @@ def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtyp
         return "the table modes"
     if heads % groups or heads // groups not in (1, 2):
         return f"heads // groups = {heads // groups if groups else 0} (supported: 1, 2)"
-    if k.shape[1] > REGION_MAX_KEYS:
-        return f"{k.shape[1]} keys (at most {REGION_MAX_KEYS})"
-    if tuple(w2.shape) != (32, 32) or tuple(w3.shape) != (heads // groups, 32):
+    if keys > REGION_MAX_KEYS:
+        return f"{keys} keys (at most {REGION_MAX_KEYS})"
+    if tuple(w2_shape) != (32, 32) or tuple(w3_shape) != (heads // groups, 32):
         return "a bias MLP other than 1 -> 32 -> 32 -> heads // groups"
     return None
 
 
-class _DeformAttnRegion1D(torch.autograd.Function):
-    """The fused core with the 1-D position bias per linear piece (include/smml.h, smml_deform_attn_region1d_*)."""
+def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtype=None, cpb_table=False, log_distance: bool = True):
+    """Why the 1-D piece path cannot take this call (None: it can)."""
+    return _region1d_why(vs.shape[-1], k.shape[1], w2.shape, w3.shape, heads, groups, compute_dtype, cpb_table, log_distance)
+
+
+def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32, 32), w3_shape=(1, 32), log_distance: bool = True,
+                compute_dtype=None, cpb_table=False, cpb_regions=None, region_pmax_given: bool = False, capturing: bool = False) -> str:
+    """The core a deform_attention call with these shapes and options takes: 'region1d' (the 1-D position bias per linear piece), 'table',
+    'pair_table_forward' (per-pair backward of a table forward), 'region' (2-D, per linear region; fp32-grade or 16-bit core) or 'pair'
+    (the per-pair MLP; fp32-grade or 16-bit core).  Raises on a combination no core supports.  No GPU work; the module switches
+    (CPB_REGIONS) are read at call time.  capturing: the call is being captured in a hipGraph (a 2-D region call then needs its pmax)."""
+    if cpb_table not in (False, True, None, "forward", "full"):
+        raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
+    if cpb_regions is not None and bool(cpb_regions) and posdim == 1:
+        # 1-D positions: the piece path only on request (cpb_regions=True), and never a silent fall-back from it
+        why = _region1d_why(posdim, keys, w2_shape, w3_shape, heads, groups, compute_dtype, cpb_table, log_distance)
+        if why is not None:
+            raise ValueError(f"cpb_regions=True with 1-D positions: the piece path does not support {why}")
+        return "region1d"
+    m16 = _dtype16(compute_dtype)
+    if cpb_table:
+        if not log_distance:
+            raise NotImplementedError("the table modes are built for the signed-log position transform only")
+        if m16 is None and cpb_table == "forward":
+            raise ValueError("cpb_table belongs to the 16-bit compute modes: pass compute_dtype='bf16' or 'fp16'")
+        if m16 is None:
+            raise ValueError("the table mode belongs to the 16-bit compute modes: pass compute_dtype='bf16' or 'fp16'")
+        return "pair_table_forward" if cpb_table == "forward" else "table"
+    if not log_distance and posdim != 1:
+        raise NotImplementedError("the raw-offset position transform (cpb_log_distance=False) exists for 1-D positions without the table modes")
+    # the position bias per linear region wherever that applies (CPB_REGIONS; cpb_regions False / True overrides it); its pmax comes from
+    # the data when not given - a host sync, impossible inside a hipGraph capture: such a call keeps the per-pair kernels
+    use_regions = CPB_REGIONS if cpb_regions is None else bool(cpb_regions)
+    if (use_regions and log_distance and posdim == 2 and heads == groups and keys <= REGION_MAX_KEYS and tuple(w3_shape) == (1, 32)
+            and (region_pmax_given or not capturing)):
+        return "region"
+    return "pair"
+
+
+# ---- shared pieces of the fused-core Functions
+def _check_core(q, heads: int, w2=None):
+    if q.shape[-1] != heads * 64:
+        raise RuntimeError("the attention kernels are built for dim_head = 64")
+    if w2 is not None and tuple(w2.shape) != (32, 32):
+        raise RuntimeError("the position-bias kernels are built for a hidden width of 32 (dim = 128)")
+
+
+def _out_lse(q, heads: int):
+    B, N, _ = q.shape
+    return torch.empty_like(q), torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
+
+
+def _score_tiles(q, heads: int, J: int, dtype, *inner):
+    """A score-shaped tensor, stored per 32-query tile (include/smml.h): [B, H, nst / 32, J, *inner, 32]."""
+    B, N, _ = q.shape
+    nst = capi.lib().smml_deform_attn_nst(N)
+    return torch.empty(B, heads, nst // 32, J, *inner, 32, device=q.device, dtype=dtype)
+
+
+def _dscores(logits, m16):
+    """The d scores of a backward: the scores' shape, fp32 (fp32-grade core) or bf16 (16-bit core)."""
+    return torch.empty(logits.shape, device=logits.device, dtype=torch.float32 if m16 is None else torch.bfloat16)
+
+
+def _grads(ctx, *grads):
+    """A backward's return: the gradients of the leading inputs, None for the rest.  dq (the first) is also parked for the offsets
+    network's backward (GradFork); it is still returned to autograd."""
+    dq = grads[0]
+    if ctx.fork is not None and ctx.needs_input_grad[0]:
+        ctx.fork.dq = dq.view(dq.shape[0], dq.shape[1], -1)
+    return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
+
+
+class _DeformAttnRegion(torch.autograd.Function):
+    """The fused core with the position bias per linear region of its MLP (include/smml.h): 2-D (csrc/cpb_regions.h; fp32-grade or, with
+    compute_dtype, the 16-bit core) or 1-D per linear piece (csrc/cpb_regions1d.h; fp32-grade core).  pmax: half-width of the tables'
+    square (2-D) / index grid (1-D; None: the span of the breakpoints); prefetch: a RegionPrefetch of the 2-D tables, if any."""
 
     @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, pmax):
-        ctx.fork = fork
-        q, k, v, vs, gq = _c(q), _c(k), _c(v), _c(vs), _c(gq)
-        w1, b1, w2, b2, w3, b3 = (_c(t) for t in (w1, b1, w2, b2, w3, b3))
-        B, N, HD = q.shape
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
+                pmax, prefetch):
+        ctx.fork, ctx.seed_offset = fork, seed_offset
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
+        B, N, _ = q.shape
         J = k.shape[1]
-        if HD != heads * 64:
-            raise RuntimeError("the attention kernels are built for dim_head = 64")
+        one_d = vs.shape[-1] == 1
+        _check_core(q, heads, w2)
         L = capi.lib()
-        tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
-        out = torch.empty_like(q)
-        lse = torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
+        m16 = _dtype16(compute_dtype)
+        if one_d:
+            tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
+        elif prefetch is not None and prefetch.matches(w1, b1, w2, b2, w3, b3, pmax):
+            tables = prefetch.join()                 # built beside the layers in front of the attention (RegionPrefetch)
+        else:
+            tables = cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax)
+        out, lse = _out_lse(q, heads)
         logits = rid = None
         if any(ctx.needs_input_grad):
-            nst = L.smml_deform_attn_nst(N)
-            logits = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.float32)
-            rid = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.int16)      # the piece of every pair, per head
-        capi.check(L.smml_deform_attn_region1d_fwd_f32(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.ptr(tables),
-                                                       capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), B, N, J, heads, groups,
-                                                       float(scale), float(dropout_p), int(dropout_seed),
-                                                       *TIMER.events("deform_region1d_fwd", B * heads * N * J), capi.stream(),
-                                                       capi.deform_opts(seed_offset)), "deform_attn_region1d_fwd")
-        ctx.seed_offset = seed_offset
-        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed))
+            logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)
+            rid = _score_tiles(q, heads, J, torch.int16)          # the linear piece of every pair, per head
+        pairs = B * heads * N * J
+        qkv = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
+        if one_d:
+            capi.check(L.smml_deform_attn_region1d_fwd_f32(*qkv, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid),
+                                                           B, N, J, heads, groups, float(scale), float(dropout_p), int(dropout_seed),
+                                                           *TIMER.events("deform_region1d_fwd", pairs), capi.stream(), capi.deform_opts(seed_offset)),
+                       "deform_attn_region1d_fwd")
+        else:
+            ropts = capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)
+            w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
+            fn, ev, name, dt = ((L.smml_deform_attn_region_fwd_f32, "deform_region_fwd", "deform_attn_region_fwd", ()) if m16 is None else
+                                (L.smml_deform_attn16_region_fwd, "deform16_region_fwd", "deform_attn16_region_fwd", (m16[0],)))
+            capi.check(fn(*qkv, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), B, N, J, heads, float(scale),
+                          float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), ropts), name)
+        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
-        if DECISION_TAP is not None:       # own key: the ids index the 1-D piece tables (region1d_tables_view), not the 2-D region tables
-            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(),
-                                 "w2": w2.detach(), "b2": b2.detach(), "masks2": None, "region1d_ids": rid, "region1d_tables": tables,
-                                 "B": B, "N": N, "J": J, "heads": heads, "groups": groups, "table_pmax": None, "log_distance": True})
+        # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
+        if DECISION_TAP is not None:
+            ids, tabs = ("region1d_ids", "region1d_tables") if one_d else ("region_ids", "tables")
+            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(), "w2": w2.detach(),
+                                 "b2": b2.detach(), "masks2": None, ids: rid, tabs: tables, "B": B, "N": N, "J": J, "heads": heads,
+                                 "groups": groups, "table_pmax": None, "log_distance": True})
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed = ctx.cfg
+        heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
         B, N, _ = q.shape
         J = k.shape[1]
         L = capi.lib()
         dout = _c(dout)
-        dlogits = torch.empty_like(logits)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        dvs = torch.empty_like(vs)
-        dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3))
-        wsb = L.smml_deform_attn_region1d_bwd_workspace_bytes(B, N, J, heads)
+        dlogits = _dscores(logits, m16)
+        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
+        pairs = B * heads * N * J
+        fwd = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
+        grads = (capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs), capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2),
+                 capi.fptr(dw3), capi.fptr(db3))
+        if vs.shape[-1] == 1:
+            wsb = L.smml_deform_attn_region1d_bwd_workspace_bytes(B, N, J, heads)
+            ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
+            capi.check(L.smml_deform_attn_region1d_bwd_f32(
+                *fwd, capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), capi.fptr(dlogits),
+                *grads, capi.ptr(ws), wsb, B, N, J, heads, groups, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region1d_bwd", pairs),
+                capi.stream(), capi.deform_opts(ctx.seed_offset)), "deform_attn_region1d_bwd")
+            return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
+        wsb = L.smml_deform_attn_region_bwd_workspace_bytes(B, N, J, heads)
         ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
-        capi.check(L.smml_deform_attn_region1d_bwd_f32(
-            capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
-            capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), capi.fptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-            capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3), capi.ptr(ws), wsb,
-            B, N, J, heads, groups, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region1d_bwd", B * heads * N * J), capi.stream(),
-            capi.deform_opts(ctx.seed_offset)), "deform_attn_region1d_bwd")
-        if ctx.fork is not None and ctx.needs_input_grad[0]:
-            ctx.fork.dq = dq.view(B, N, -1)
-        return dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None, None, None, None, None
+        w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
+        fn, ev, name, dt = ((L.smml_deform_attn_region_bwd_f32, "cpb_region_bwd", "deform_attn_region_bwd", ()) if m16 is None else
+                            (L.smml_deform_attn16_region_bwd, "cpb16_region_bwd", "deform_attn16_region_bwd", (m16[0],)))
+        capi.check(fn(*fwd, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits),
+                      *grads, capi.ptr(ws), wsb, B, N, J, heads, scale, dropout_p, dropout_seed, *dt, *TIMER.events(ev, pairs), capi.stream(),
+                      capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
+        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
 
 _REGION_STREAMS = {}
@@ -1080,102 +1173,51 @@ class RegionPrefetch:
         return self.tables
 
 
-class _DeformAttn(torch.autograd.Function):
+class _DeformAttnPair(torch.autograd.Function):
+    """The fused core with the per-pair position-bias MLP (csrc/deform_attn.hip; with compute_dtype csrc/deform_attn16.hip).
+    table_pmax_fwd (cpb_table='forward', 16-bit): the forward takes its bias from the table, the backward takes layer 2's decisions from
+    a mask table (or recomputes them per pair: TABLE_FORWARD_MASKS)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset=None,
-                compute_dtype=None, fork=None, table_pmax_fwd=None, log_distance=True, region_pmax=None, region_prefetch=None):
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
+                table_pmax_fwd, log_distance):
         ctx.fork = fork
+        ctx.seed_offset = seed_offset           # a device int64 [1] owned by this call (hipGraph replays: deform_attention)
         ctx.log_distance = bool(log_distance)
-        if not log_distance and (vs.shape[-1] != 1 or table_pmax_fwd is not None):
-            raise NotImplementedError("the raw-offset position transform (cpb_log_distance=False) exists for 1-D positions without the table modes")
-        q, k, v, vs, gq = _c(q), _c(k), _c(v), _c(vs), _c(gq)
-        w1, b1, w2, b2, w3, b3 = (_c(t) for t in (w1, b1, w2, b2, w3, b3))
-        B, N, HD = q.shape
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
+        B, N, _ = q.shape
         J = k.shape[1]
         posdim = vs.shape[-1]
-        if HD != heads * 64:
-            raise RuntimeError("the attention kernels are built for dim_head = 64")
-        if tuple(w2.shape) != (32, 32):
-            raise RuntimeError("the position-bias kernels are built for a hidden width of 32 (dim = 128)")
+        _check_core(q, heads, w2)
         L = capi.lib()
         m16 = _dtype16(compute_dtype)
-        out = torch.empty_like(q)
-        lse = torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
-        need_grad = any(ctx.needs_input_grad)
+        out, lse = _out_lse(q, heads)
         logits = masks = None
-        tabfwd = table_pmax_fwd is not None           # 16-bit mode, forward bias from the table; the backward takes layer 2's decisions from a mask table
-        ctx.table_pmax = table_pmax_fwd               # (or recomputes layer 2 per pair: TABLE_FORWARD_MASKS)
+        tabfwd = table_pmax_fwd is not None
+        ctx.table_pmax = table_pmax_fwd
         ctx.export_masks = None
-        regions = (region_pmax is not None and not tabfwd and posdim == 2 and log_distance and heads == groups
-                   and J <= REGION_MAX_KEYS and tuple(w3.shape) == (1, 32))        # fp32-grade core or (m16) the 16-bit core, same lookup
-        ctx.regions = regions
-        if regions:
-            if region_prefetch is not None and region_prefetch.matches(w1, b1, w2, b2, w3, b3, region_pmax):
-                tables = region_prefetch.join()                 # built beside the layers in front of the attention (RegionPrefetch)
-            else:
-                tables = cpb_regions_build(w1, b1, w2, b2, w3, b3, region_pmax)
-            rid = None
-            if need_grad:
-                nst = L.smml_deform_attn_nst(N)
-                logits = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.float32 if m16 is None else torch.float16)
-                rid = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.int16)      # the linear piece of every pair
-            ropts = capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)
-            if m16 is None:
-                capi.check(L.smml_deform_attn_region_fwd_f32(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq),
-                                                             capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.fptr(w3),
-                                                             capi.fptr(b3), capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.fptr(logits),
-                                                             capi.ptr(rid), B, N, J, heads, float(scale), float(dropout_p), int(dropout_seed),
-                                                             *TIMER.events("deform_region_fwd", B * heads * N * J), capi.stream(), ropts),
-                           "deform_attn_region_fwd")
-            else:
-                capi.check(L.smml_deform_attn16_region_fwd(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq),
-                                                           capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.fptr(w3),
-                                                           capi.fptr(b3), capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits),
-                                                           capi.ptr(rid), B, N, J, heads, float(scale), float(dropout_p), int(dropout_seed),
-                                                           m16[0], *TIMER.events("deform16_region_fwd", B * heads * N * J), capi.stream(), ropts),
-                           "deform_attn16_region_fwd")
-            ctx.seed_offset = seed_offset
-            ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
-            ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
-            if DECISION_TAP is not None:
-                DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(),
-                                     "w2": w2.detach(), "b2": b2.detach(), "masks2": None, "region_ids": rid, "tables": tables,
-                                     "B": B, "N": N, "J": J, "heads": heads, "groups": groups, "table_pmax": None, "log_distance": True})
-            return out
-        if need_grad:
-            nst = L.smml_deform_attn_nst(N)
-            # score-shaped tensors are stored per 32-query tile (include/smml.h): [B, H, nst / 32, J, 32] (+ the lane-half axis of the masks)
-            logits = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.float32 if m16 is None else torch.float16)   # 16-bit mode: fp16 scores in both sub-modes
+        if any(ctx.needs_input_grad):
+            logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)   # 16-bit mode: fp16 scores in both sub-modes
             if not tabfwd:
-                masks = torch.empty(B, heads, nst // 32, J, 2, 32, device=q.device, dtype=torch.int16)   # layer-2 ReLU decisions of the bias MLP
+                masks = _score_tiles(q, heads, J, torch.int16, 2)           # layer-2 ReLU decisions of the bias MLP (per lane half)
             elif DECISION_TAP is not None:            # tests: the backward writes the decisions it recomputed here
-                ctx.export_masks = torch.zeros(B, heads, nst // 32, J, 2, 32, device=q.device, dtype=torch.int16)
+                ctx.export_masks = _score_tiles(q, heads, J, torch.int16, 2).zero_()
         opts = capi.deform_opts(seed_offset, ctx.log_distance)
+        pairs = B * heads * N * J
+        qkv = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
+        w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
         if tabfwd:
-            if m16 is None:
-                raise ValueError("cpb_table belongs to the 16-bit compute modes: pass compute_dtype='bf16' or 'fp16'")
             points = L.smml_deform_attn_table_points(posdim)
             with torch.no_grad():
                 table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=posdim, pmax=table_pmax_fwd, device=q.device)
-            capi.check(L.smml_deform_attn_table_fwd(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(table),
-                                                    capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups, posdim, points,
-                                                    float(table_pmax_fwd), float(scale), float(dropout_p), int(dropout_seed), m16[0],
-                                                    *TIMER.events("deform_table_fwd", B * heads * N * J), capi.stream(), opts), "deform_attn_table_fwd")
-        elif m16 is None:
-            capi.check(L.smml_deform_attn_fwd_f32(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq),
-                                                  capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.fptr(w3),
-                                                  capi.fptr(b3), capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.ptr(masks), B, N, J,
-                                                  heads, groups, posdim, float(scale), float(dropout_p), int(dropout_seed),
-                                                  *TIMER.events("deform_attn_fwd", B * heads * N * J), capi.stream(), opts),
-                       "deform_attn_fwd")
+            capi.check(L.smml_deform_attn_table_fwd(*qkv, capi.fptr(table), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups,
+                                                    posdim, points, float(table_pmax_fwd), float(scale), float(dropout_p), int(dropout_seed), m16[0],
+                                                    *TIMER.events("deform_table_fwd", pairs), capi.stream(), opts), "deform_attn_table_fwd")
         else:
-            capi.check(L.smml_deform_attn16_fwd(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq),
-                                                capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.fptr(w3),
-                                                capi.fptr(b3), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(masks), B, N, J,
-                                                heads, groups, posdim, float(scale), float(dropout_p), int(dropout_seed), m16[0],
-                                                *TIMER.events("deform16_fwd", B * heads * N * J), capi.stream(), opts),
-                       "deform_attn16_fwd")
-        ctx.seed_offset = seed_offset           # a device int64 [1] owned by this call (hipGraph replays: deform_attention)
+            fn, ev, name, dt = ((L.smml_deform_attn_fwd_f32, "deform_attn_fwd", "deform_attn_fwd", ()) if m16 is None else
+                                (L.smml_deform_attn16_fwd, "deform16_fwd", "deform_attn16_fwd", (m16[0],)))
+            capi.check(fn(*qkv, *w, capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(masks), B, N, J, heads, groups, posdim, float(scale),
+                          float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), opts), name)
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, masks)
         if DECISION_TAP is not None:
@@ -1186,8 +1228,6 @@ class _DeformAttn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        if ctx.regions:
-            return _DeformAttn._backward_regions(ctx, dout)
         q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, masks = ctx.saved_tensors
         heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
         B, N, _ = q.shape
@@ -1195,21 +1235,18 @@ class _DeformAttn(torch.autograd.Function):
         posdim = vs.shape[-1]
         L = capi.lib()
         dout = _c(dout)
-        dlogits = torch.empty_like(logits) if m16 is None else torch.empty(logits.shape, device=q.device, dtype=torch.bfloat16)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        dvs = torch.empty_like(vs)
-        dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3))
+        dlogits = _dscores(logits, m16)
+        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
         wsb = L.smml_deform_attn_bwd_workspace_bytes(B, N, J, heads)
         ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
+        pairs = B * heads * N * J
+        fwd = [capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, dout, lse)]
+        grads = [capi.fptr(t) for t in (dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3)]
         if m16 is None:
             capi.check(L.smml_deform_attn_bwd_f32(
-                capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(w1), capi.fptr(b1),
-                capi.fptr(w2), capi.fptr(b2), capi.fptr(w3), capi.fptr(b3), capi.fptr(out), capi.fptr(dout), capi.fptr(lse),
-                capi.fptr(logits), capi.ptr(masks), capi.fptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-                capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3),
-                capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale, dropout_p, dropout_seed,
-                *TIMER.events("cpb_bwd", B * heads * N * J),
-                capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance)), "deform_attn_bwd")
+                *fwd, capi.fptr(logits), capi.ptr(masks), capi.fptr(dlogits), *grads, capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale,
+                dropout_p, dropout_seed, *TIMER.events("cpb_bwd", pairs), capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance)),
+                "deform_attn_bwd")
         else:
             mtab = None
             if masks is None and TABLE_FORWARD_MASKS == "table":
@@ -1219,54 +1256,10 @@ class _DeformAttn(torch.autograd.Function):
                 capi.check(L.smml_cpb_mask_table(capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.ptr(mtab), posdim,
                                                  float(ctx.table_pmax), capi.stream()), "cpb_mask_table")
             capi.check(L.smml_deform_attn16_bwd(
-                capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(w1), capi.fptr(b1),
-                capi.fptr(w2), capi.fptr(b2), capi.fptr(w3), capi.fptr(b3), capi.fptr(out), capi.fptr(dout), capi.fptr(lse),
-                capi.ptr(logits), capi.ptr(masks), capi.ptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-                capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3),
-                capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale, dropout_p, dropout_seed, m16[0],
-                *TIMER.events("cpb16_bwd", B * heads * N * J),
-                capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)),
-                "deform_attn16_bwd")
-        if ctx.fork is not None and ctx.needs_input_grad[0]:
-            ctx.fork.dq = dq.view(B, N, -1)          # parked for the offsets network's backward (GradFork); still returned to autograd
-        return dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None, None, None, None, None, None, None, None, None
-
-    @staticmethod
-    def _backward_regions(ctx, dout):
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed, _ = ctx.cfg
-        B, N, _ = q.shape
-        J = k.shape[1]
-        L = capi.lib()
-        dout = _c(dout)
-        m16 = ctx.cfg[5]
-        dlogits = torch.empty_like(logits) if m16 is None else torch.empty(logits.shape, device=q.device, dtype=torch.bfloat16)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        dvs = torch.empty_like(vs)
-        dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3))
-        wsb = L.smml_deform_attn_region_bwd_workspace_bytes(B, N, J, heads)
-        ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
-        if m16 is not None:
-            capi.check(L.smml_deform_attn16_region_bwd(
-                capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(w1), capi.fptr(b1), capi.fptr(w2),
-                capi.fptr(b2), capi.fptr(w3), capi.fptr(b3), capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse),
-                capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-                capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3), capi.ptr(ws), wsb,
-                B, N, J, heads, scale, dropout_p, dropout_seed, m16[0], *TIMER.events("cpb16_region_bwd", B * heads * N * J), capi.stream(),
-                capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), "deform_attn16_region_bwd")
-            if ctx.fork is not None and ctx.needs_input_grad[0]:
-                ctx.fork.dq = dq.view(B, N, -1)
-            return dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None, None, None, None, None, None, None, None, None
-        capi.check(L.smml_deform_attn_region_bwd_f32(
-            capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(w1), capi.fptr(b1), capi.fptr(w2),
-            capi.fptr(b2), capi.fptr(w3), capi.fptr(b3), capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse),
-            capi.fptr(logits), capi.ptr(rid), capi.fptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-            capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2), capi.fptr(dw3), capi.fptr(db3), capi.ptr(ws), wsb,
-            B, N, J, heads, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region_bwd", B * heads * N * J), capi.stream(),
-            capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), "deform_attn_region_bwd")
-        if ctx.fork is not None and ctx.needs_input_grad[0]:
-            ctx.fork.dq = dq.view(B, N, -1)
-        return dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3, None, None, None, None, None, None, None, None, None, None, None, None
+                *fwd, capi.ptr(logits), capi.ptr(masks), capi.ptr(dlogits), *grads, capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale,
+                dropout_p, dropout_seed, m16[0], *TIMER.events("cpb16_bwd", pairs), capi.stream(),
+                capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)), "deform_attn16_bwd")
+        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1303,35 +1296,30 @@ def cpb_table_fn(w1, b1, w2, b2, w3, b3, *, posdim: int, pmax: float, device):
 
 
 class _DeformAttnTable(torch.autograd.Function):
+    """The 16-bit core with the position bias interpolated from `table` (include/smml.h, table mode); differentiates the table, which
+    cpb_table_fn carries back to the MLP."""
+
     @staticmethod
     def forward(ctx, q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork, pmax, grid):
-        ctx.fork = fork
+        ctx.fork, ctx.seed_offset = fork, seed_offset
         ctx.grid = tuple(int(x) for x in grid) if grid else (0, 0)
         q, k, v, vs, gq, table = _c(q), _c(k), _c(v), _c(vs), _c(gq), _c(table)
-        B, N, HD = q.shape
+        B, N, _ = q.shape
         J = k.shape[1]
         posdim = vs.shape[-1]
-        if HD != heads * 64:
-            raise RuntimeError("the attention kernels are built for dim_head = 64")
+        _check_core(q, heads)
         L = capi.lib()
         m16 = _dtype16(compute_dtype)
-        if m16 is None:
-            raise ValueError("the table mode belongs to the 16-bit compute modes: pass compute_dtype='bf16' or 'fp16'")
         points = L.smml_deform_attn_table_points(posdim)
         if tuple(table.shape) != (heads // groups, points ** posdim):
             raise RuntimeError(f"table must be [{heads // groups}, {points ** posdim}] (got {tuple(table.shape)})")
-        out = torch.empty_like(q)
-        lse = torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
-        logits = None
-        if any(ctx.needs_input_grad):
-            nst = L.smml_deform_attn_nst(N)
-            logits = torch.empty(B, heads, nst // 32, J, 32, device=q.device, dtype=torch.float16)
+        out, lse = _out_lse(q, heads)
+        logits = _score_tiles(q, heads, J, torch.float16) if any(ctx.needs_input_grad) else None
         capi.check(L.smml_deform_attn_table_fwd(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(table),
                                                 capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups, posdim, points,
                                                 float(pmax), float(scale), float(dropout_p), int(dropout_seed), m16[0],
                                                 *TIMER.events("deform_table_fwd", B * heads * N * J), capi.stream(), capi.deform_opts(seed_offset)),
                    "deform_attn_table_fwd")
-        ctx.seed_offset = seed_offset
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16, points, float(pmax))
         ctx.save_for_backward(q, k, v, vs, gq, table, out, lse, logits)
         if DECISION_TAP is not None:       # no per-pair ReLU decisions in this mode: the MLP runs on grid points only
@@ -1348,8 +1336,8 @@ class _DeformAttnTable(torch.autograd.Function):
         posdim = vs.shape[-1]
         L = capi.lib()
         dout = _c(dout)
-        dlogits = torch.empty(logits.shape, device=q.device, dtype=torch.bfloat16)
-        dq, dk, dv, dvs, dtable = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(vs), torch.empty_like(table)
+        dlogits = _dscores(logits, m16)
+        dq, dk, dv, dvs, dtable = (torch.empty_like(t) for t in (q, k, v, vs, table))
         wsb = L.smml_deform_attn_table_bwd_workspace_bytes(B, N, J, heads, posdim)
         ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
         capi.check(L.smml_deform_attn_table_bwd(
@@ -1358,9 +1346,7 @@ class _DeformAttnTable(torch.autograd.Function):
             capi.fptr(dtable), capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, points, pmax, ctx.grid[0], ctx.grid[1], scale, dropout_p,
             dropout_seed, m16[0],
             *TIMER.events("cpb_table_bwd", B * heads * N * J), capi.stream(), capi.deform_opts(ctx.seed_offset)), "deform_attn_table_bwd")
-        if ctx.fork is not None and ctx.needs_input_grad[0]:
-            ctx.fork.dq = dq.view(B, N, -1)
-        return dq, dk, dv, dvs, None, dtable, None, None, None, None, None, None, None, None, None, None
+        return _grads(ctx, dq, dk, dv, dvs, None, dtable)
 
 
 def table_pmax(gq_bound: float, vs_bound: float) -> float:
@@ -1410,40 +1396,27 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
     cpb_regions True with 1-D positions: the position bias per linear piece of its MLP (csrc/cpb_regions1d.h; signed-log offsets, the
     fp32-grade core, heads // groups in {1, 2}; anything else raises), cpb_region_pmax = half-width of its index grid (None: the span of
     the breakpoints; no host sync either way)."""
-    if cpb_table not in (False, True, None, "forward", "full"):
-        raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
-    if cpb_regions is not None and bool(cpb_regions) and vs.shape[-1] == 1:
-        # 1-D positions: the piece path only on request (cpb_regions=True), and never a silent fall-back from it
-        why = region1d_unsupported(vs, k, w2, w3, heads=heads, groups=groups, compute_dtype=compute_dtype, cpb_table=cpb_table,
-                                   log_distance=log_distance)
-        if why is not None:
-            raise ValueError(f"cpb_regions=True with 1-D positions: the piece path does not support {why}")
-        return _DeformAttnRegion1D.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                         dropout_seed_offset, fork, cpb_region_pmax)
-    if cpb_table and cpb_table_pmax is None:
+    path = deform_path(posdim=vs.shape[-1], heads=heads, groups=groups, keys=k.shape[1], w2_shape=w2.shape, w3_shape=w3.shape,
+                       log_distance=log_distance, compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions,
+                       region_pmax_given=cpb_region_pmax is not None,
+                       capturing=cpb_region_pmax is None and q.is_cuda and torch.cuda.is_current_stream_capturing())
+    if path in ("region", "region1d"):
+        pmax = cpb_region_pmax
+        if path == "region" and pmax is None:      # from the data: one host sync
+            pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
+        return _DeformAttnRegion.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
+                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None)
+    if path == "pair":
+        return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
+                                     dropout_seed_offset, compute_dtype, fork, None, log_distance)
+    if cpb_table_pmax is None:
         cpb_table_pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
-    if cpb_table and not log_distance:
-        raise NotImplementedError("the table modes are built for the signed-log position transform only")
-    if cpb_table == "forward":
-        return _DeformAttn.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                 dropout_seed_offset, compute_dtype, fork, cpb_table_pmax)
-    if cpb_table:
-        posdim = vs.shape[-1]
-        table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=posdim, pmax=cpb_table_pmax, device=q.device)
-        return _DeformAttnTable.apply(q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, dropout_seed_offset,
-                                      compute_dtype, fork, cpb_table_pmax, cpb_table_grid)
-    # fp32-grade path: the position bias per linear region of its MLP wherever that applies (see CPB_REGIONS); cpb_regions False / True
-    # overrides the default, cpb_region_pmax = half-width of the tabulated square in signed-log units (None: from the data, one host sync)
-    use_regions = CPB_REGIONS if cpb_regions is None else bool(cpb_regions)
-    region_pmax = None
-    if (use_regions and log_distance and vs.shape[-1] == 2 and heads == groups and k.shape[1] <= REGION_MAX_KEYS
-            and tuple(w3.shape) == (1, 32)):
-        if cpb_region_pmax is not None:
-            region_pmax = cpb_region_pmax
-        elif not torch.cuda.is_current_stream_capturing():         # from the data: a host sync, impossible inside a hipGraph capture - such a
-            region_pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))   # call keeps the per-pair kernels
-    return _DeformAttn.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                             dropout_seed_offset, compute_dtype, fork, None, log_distance, region_pmax, cpb_region_prefetch)
+    if path == "pair_table_forward":
+        return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
+                                     dropout_seed_offset, compute_dtype, fork, cpb_table_pmax, log_distance)
+    table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=vs.shape[-1], pmax=cpb_table_pmax, device=q.device)
+    return _DeformAttnTable.apply(q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, dropout_seed_offset,
+                                  compute_dtype, fork, cpb_table_pmax, cpb_table_grid)
 
 
 def deform_attention_dropout_mask(B: int, N: int, J: int, H: int, dropout_p: float, dropout_seed: int, device, seed_offset=None):

@@ -21,10 +21,12 @@ ob = Fh._Sample.backward
 def sb(ctx, dkv):
     r = ob(ctx, dkv); cap["sampler"] = r[1].detach().clone(); return r
 Fh._Sample.backward = staticmethod(sb)
-oa = Fh._DeformAttn.backward
-def ab(ctx, dout):
-    r = oa(ctx, dout); cap["cpb"] = r[3].detach().clone(); return r
-Fh._DeformAttn.backward = staticmethod(ab)
+def tap_dvs(fn):
+    orig = fn.backward
+    def ab(ctx, dout):
+        r = orig(ctx, dout); cap["cpb"] = r[3].detach().clone(); return r
+    fn.backward = staticmethod(ab)
+tap_dvs(Fh._DeformAttnPair); tap_dvs(Fh._DeformAttnRegion)
 enc, logits, _, omic_t, vg = net.pathomic_net_tumor(x_path.to(cuda), net.omic_net_tumor(x_omic=x_o.to(cuda))[0])
 (enc * w_enc.to(cuda)).sum().backward()
 tot = (cap["sampler"] + cap["cpb"]).cpu().double()
