@@ -279,6 +279,44 @@ int smml_deform_attn16_region_bwd(const float* q, const float* k, const float* v
                                   unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
                                   const SmmlDeformOpts* opts);
 
+/* The region path with ONE OR TWO heads per offset group (H / G in {1, 2}; the MLP of DeformableAttention2D.py:129-152 then ends in
+ * Linear(32, H / G)).  Both outputs share layers 1 and 2, so they share the regions, the lookup and the region ids; only (a, c) differs per
+ * output.  smml_cpb_regions_mh_build tabulates the same regions as smml_cpb_regions_build plus, for outputs == 2, the (a, c) of the second
+ * output (w3 [outputs, 32], b3 [outputs]; same buffer size, smml_cpb_regions_bytes()).  In the forward and backward, head h belongs to
+ * offset group h / (H / G), reads that group's sample positions vs [(B G), J, 2] and takes output h % (H / G); d vs of a group is the sum
+ * over its heads.  region_ids [B, H, nst / 32, J, 32]: per head (the heads of a group hold equal ids).  The tables must have been built
+ * with outputs = H / G.  Workspace of the backwards: smml_deform_attn_region_mh_bwd_workspace_bytes, 256-byte aligned.  With H == G every
+ * output is bit-identical to the one-output entry points above.  A non-finite d score makes the six parameter gradients NaN.  Every
+ * output is run-to-run identical. */
+int smml_cpb_regions_mh_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int outputs,
+                              float pmax, void* tables, size_t tables_bytes, void* stream);
+int smml_deform_attn_region_mh_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                       float* out, float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                       float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream,
+                                       const SmmlDeformOpts* opts);
+size_t smml_deform_attn_region_mh_bwd_workspace_bytes(int B, int N, int J, int H, int G);
+int smml_deform_attn_region_mh_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                       const float* out, const float* dout, const float* lse, const float* logits_t,
+                                       const unsigned short* region_ids, float* dlogits_t, float* dq, float* dk, float* dv, float* dvs, float* dw1,
+                                       float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B,
+                                       int N, int J, int H, int G, float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start,
+                                       void* ev_stop, void* stream, const SmmlDeformOpts* opts);
+int smml_deform_attn16_region_mh_fwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                     const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                     float* out, float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                     float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop,
+                                     void* stream, const SmmlDeformOpts* opts);
+int smml_deform_attn16_region_mh_bwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                     const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                     const float* out, const float* dout, const float* lse, const unsigned short* logits16,
+                                     const unsigned short* region_ids, unsigned short* dlogits16, float* dq, float* dk, float* dv, float* dvs,
+                                     float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                                     size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p,
+                                     unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
+                                     const SmmlDeformOpts* opts);
+
 /* 16-bit compute mode of the same fused core (csrc/deform_attn16.hip; BASELINE config 4 names bf16, config 5 fp16): the op sequence of
  * smml_deform_attn_fwd_f32 / _bwd_f32 (models/DeformableAttention2D.py:120-157,284-312; DeformableAttention1D.py:60-102,205-232) with
  * single-term 16-bit operands on the matrix pipe - dtype 0 = bf16, 1 = fp16 for forward-range operands (q, k, v, probabilities, the

@@ -56,7 +56,7 @@ struct RegionHeader {                    // first 256 bytes of the table buffer
 
 // byte offsets inside the table buffer (all multiples of 256)
 struct RegionLayout {
-  size_t hdr, reg, pat, t0h, t1h, edge, t0, t1, ekey, hkey, hid, sublist, cand, klist, corners, subcorners, wd, total;
+  size_t hdr, reg, pat, t0h, t1h, edge, t0, t1, ekey, hkey, hid, sublist, cand, klist, corners, subcorners, wd, reg1, total;
 };
 __host__ __device__ inline RegionLayout region_layout() {
   RegionLayout l;
@@ -80,7 +80,9 @@ __host__ __device__ inline RegionLayout region_layout() {
   l.klist = take((size_t)RG_HASH * 8 + (size_t)RG_HASH * 4);   // compacted keys, then their slots
   l.corners = take((size_t)(RG_G + 1) * (RG_G + 1) * 8);
   l.subcorners = take((size_t)RG_SUBCAP * RG_SUBC * 8);        // ReLU patterns at the 9 x 9 corners of every refined cell
-  l.wd = take(1200 * 8);                                    // the MLP's parameters in fp64
+  l.wd = take(1232 * 8);                                    // the MLP's parameters in fp64
+  // two heads per offset group (the second output of the MLP): its (a0, a1, c) per region, after every block the one-output tables use
+  l.reg1 = take((size_t)RG_RCAP * 16);                      // float4 {a0, a1, c, 0} per region
   l.total = o;
   return l;
 }
@@ -105,8 +107,16 @@ inline RegionTables region_tables(void* base) {
   return t;
 }
 
-// fp64 copy of the parameters: w1 [32][2] at 0, b1 at 64, w2 [32][32] at 96, b2 at 1120, w3 at 1152, b3 at 1184
+// (a0, a1, c) of output 1 (region_layout().reg1): from the base of a table buffer (its header), a compile-time offset
+__host__ __device__ inline const float4* region_reg1(const RegionHeader* hdr) {
+  return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(hdr) + region_layout().reg1);
+}
+
+// fp64 copy of the parameters: w1 [32][2] at 0, b1 at 64, w2 [32][32] at 96, b2 at 1120, w3 at 1152, b3 at 1184; with two outputs
+// (two heads per offset group) row 1 of w3 at 1185 and b3 [1] at 1217
 constexpr int WD_W1 = 0, WD_B1 = 64, WD_W2 = 96, WD_B2 = 1120, WD_W3 = 1152, WD_B3 = 1184, WD_N = 1185;
+constexpr int WD_W3B = 1185, WD_B3B = 1217, WD_N2 = 1218;
+static_assert(WD_N2 <= 1232, "region_layout().wd");
 
 __global__ void region_prep_kernel(CpbParams cp, float pmax, RegionTables t) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,6 +135,12 @@ __global__ void region_prep_kernel(CpbParams cp, float pmax, RegionTables t) {
   }
   for (int s = i; s < RG_HASH; s += gridDim.x * blockDim.x) t.hkey[s] = RG_EMPTY;
   for (int s = i; s < RG_EDGES; s += gridDim.x * blockDim.x) t.ekey[s] = 0xFFFFFFFFu;
+}
+// the second output's w3 row and b3 (two heads per offset group; the layer-1 / layer-2 tables do not depend on them)
+__global__ void region_prep2_kernel(CpbParams cp, RegionTables t) {
+  const int i = threadIdx.x;
+  if (i < CH) t.wd[WD_W3B + i] = (double)cp.w3[CH + i];
+  else if (i == CH) t.wd[WD_B3B] = (double)cp.b3[1];
 }
 
 // ReLU patterns of the MLP at p in fp64, "natural" evaluation (every unit decides by its own pre-activation).  wd: uniform address
@@ -428,6 +444,24 @@ __global__ __launch_bounds__(256) void region_coef_kernel(RegionTables t) {
   for (int off = 16; off > 0; off >>= 1) { a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); c += __shfl_xor(c, off); }
   if ((threadIdx.x & 63) == 0) t.reg[r] = make_float4((float)a0, (float)a1, (float)(c + wd[WD_B3]), 0.f);
 }
+// the same for the second output (two heads per offset group): its w3 row and b3, into region_layout().reg1
+__global__ __launch_bounds__(256) void region_coef1_kernel(RegionTables t) {
+  const unsigned r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= t.hdr->n_regions) return;
+  const int i = threadIdx.x & 31;
+  const double* __restrict__ wd = t.wd;
+  const unsigned long long k = t.pat[r];
+  const unsigned d1 = (unsigned)k, d2 = (unsigned)(k >> 32);
+  double c1 = 0.0;
+  for (int o = 0; o < CH; ++o)
+    if ((d2 >> o) & 1u) c1 = fma(wd[WD_W2 + o * CH + i], wd[WD_W3B + o], c1);
+  c1 = ((d1 >> i) & 1u) ? c1 : 0.0;
+  double a0 = c1 * wd[WD_W1 + 2 * i], a1 = c1 * wd[WD_W1 + 2 * i + 1];
+  double c = fma(c1, wd[WD_B1 + i], ((d2 >> i) & 1u) ? wd[WD_W3B + i] * wd[WD_B2 + i] : 0.0);
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) { a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); c += __shfl_xor(c, off); }
+  if ((threadIdx.x & 63) == 0) const_cast<float4*>(region_reg1(t.hdr))[r] = make_float4((float)a0, (float)a1, (float)(c + wd[WD_B3B]), 0.f);
+}
 // hash slots -> dense ids: the 16-bit cell codes the attention kernels read, and the region fields of the records
 __device__ __forceinline__ unsigned short region_code(const RegionTables& t, unsigned e) {
   const unsigned kind = e >> 30, pay = e & RG_PAYLOAD;
@@ -452,9 +486,11 @@ __global__ __launch_bounds__(256) void region_remap_kernel(RegionTables t) {
   }
 }
 
-static int region_build_launch(CpbParams cp, float pmax, void* tables, hipStream_t st) {
+// outputs: of the MLP's last layer (heads per offset group), 1 or 2; the second output adds its (a, c) table (region_layout().reg1)
+static int region_build_launch(CpbParams cp, float pmax, void* tables, hipStream_t st, int outputs = 1) {
   const RegionTables t = region_tables(tables);
   hipLaunchKernelGGL(region_prep_kernel, dim3(64), dim3(256), 0, st, cp, pmax, t);
+  if (outputs == 2) hipLaunchKernelGGL(region_prep2_kernel, dim3(1), dim3(64), 0, st, cp, t);
   constexpr int GP = RG_G + 1;
   hipLaunchKernelGGL(region_corners_kernel, dim3((GP * GP + 255) / 256), dim3(256), 0, st, t);
   hipLaunchKernelGGL(region_classify0_kernel, dim3(RG_G * RG_G / 256), dim3(256), 0, st, t);
@@ -465,6 +501,7 @@ static int region_build_launch(CpbParams cp, float pmax, void* tables, hipStream
   hipLaunchKernelGGL(region_compact_kernel, dim3(RG_HASH / 256), dim3(256), 0, st, t);
   hipLaunchKernelGGL(region_rank_kernel, dim3(RG_HASH / 256), dim3(256), 0, st, t);
   hipLaunchKernelGGL(region_coef_kernel, dim3(RG_RCAP / 4), dim3(256), 0, st, t);
+  if (outputs == 2) hipLaunchKernelGGL(region_coef1_kernel, dim3(RG_RCAP / 4), dim3(256), 0, st, t);
   const size_t nmax = (size_t)RG_G * RG_G + (size_t)RG_SUBCAP * RG_SUB * RG_SUB + RG_EDGES;
   hipLaunchKernelGGL(region_remap_kernel, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, st, t);
   return 0;
@@ -537,19 +574,22 @@ __device__ __forceinline__ float coop_mlp_fwd(const CoopMlp& m, float p0, float 
 }
 
 // ------------------------------------------------------------------------------------------------
-// forward, position bias per linear region (PD = 2, signed-log offsets, one head per offset group)
+// forward, position bias per linear region (PD = 2, signed-log offsets; MH: one or two heads per offset group, else one)
 // ------------------------------------------------------------------------------------------------
 // T = float: the fp32-grade core (fp16 hi / lo split products, fp32 scores saved).  T = __bf16 / _Float16: the 16-bit compute mode of
 // deform_attn16.hip (single-term T operands, scores saved as fp16 and the forward's own softmax continued on the ROUNDED scores) - the
 // position bias is the same fp32 lookup in every mode.
 template <typename T> struct RegionScore { typedef u16 type; };
 template <> struct RegionScore<float> { typedef float type; };
-template <bool SAVE, typename T = float>
+// MH (G offset groups of H / G in {1, 2} heads): head h belongs to group h / (H / G), whose sample positions it reads, and takes output
+// h % (H / G) of the MLP - the (a, c) table of that output, its row of w3 and its b3.  The regions themselves (layers 1 and 2) are shared.
+// Without MH, G is not read (one head per offset group).
+template <bool SAVE, typename T = float, bool MH = false>
 __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, const float* __restrict__ VS,
     const float* __restrict__ GQ, CpbParams cp, RegionView rv, float* __restrict__ O, float* __restrict__ LSE,
     typename RegionScore<T>::type* __restrict__ LT, unsigned short* __restrict__ RID, int N, int J, int H, int NST, float scale, DropCfg dc_in,
-    int lcap) {
+    int lcap, int G) {
   constexpr bool F32 = std::is_same<T, float>::value;
   typedef typename std::conditional<F32, _Float16, T>::type T16;        // element type of the single-term operands (unused for F32)
   typedef typename Vec8<T16>::type vec8;
@@ -568,11 +608,13 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
   const int HD = H * DH;
   const bool qvalid = (q0 + c) < N;
   const int qi = qvalid ? (q0 + c) : (N - 1);
-  const float* VSb = VS + (size_t)(b * H + h) * J * 2;                       // one head per offset group: group = head
+  const int hpg = MH ? H / G : 1, g = MH ? h / hpg : h, oi = MH ? h - g * hpg : 0;
+  const float* VSb = VS + (size_t)(b * (MH ? G : H) + g) * J * 2;            // the sample positions of the head's offset group
+  const float4* __restrict__ regs = (MH && oi) ? region_reg1(rv.hdr) : rv.reg;   // (a0, a1, c) of the head's output
 
   {
     const int nreg = min((int)rv.hdr->n_regions, lcap);       // lcap <= RG_LCAP: regions resident in LDS (tests lower it)
-    for (int i = tid; i < nreg; i += 256) regl[i] = rv.reg[i];
+    for (int i = tid; i < nreg; i += 256) regl[i] = regs[i];
     for (int i = tid; i < CH * CH; i += 256) w2t[(i & 31) * CH + (i >> 5)] = cp.w2[i];      // i = o * 32 + in
     if (tid < KT) {
       const int key = min(tid, J - 1);
@@ -582,7 +624,7 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
   }
   __syncthreads();
   const float cs = rv.hdr->cs, co = rv.hdr->co;
-  const CoopMlp mlp{cp.w1[c * 2], cp.w1[c * 2 + 1], cp.b1[c], cp.b2[c], cp.w3[c], cp.b3[0], w2t, nullptr};
+  const CoopMlp mlp{cp.w1[c * 2], cp.w1[c * 2 + 1], cp.b1[c], cp.b2[c], cp.w3[oi * CH + c], cp.b3[oi], w2t, nullptr};
 
   // scaled Q of this lane's query as the B operand of S^T = K . Q^T: k-step st holds d = 16 st + 8 hf + j, fp16 hi / lo
   half8 qh[4], ql[4];
@@ -769,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
         const bool kin = acc_row(r, hf) < nk;
         if (idr == RG_NONE) nonemask |= kin ? (1u << r) : 0u;
         else if (idr >= (unsigned)lcap) {      // a region beyond the LDS-resident ones (none for up to RG_LCAP regions): from global memory
-          const float4 ac = rv.reg[idr];
+          const float4 ac = regs[idr];
           s[r] += fmaf(ac.x, p0[r], fmaf(ac.y, p1[r], ac.z));
         }
       }
@@ -970,29 +1012,36 @@ struct RegionBwdLds {                    // dynamic LDS of cpb_region_bwd_kernel
 // the region's LDS accumulators with three 64-bit integer adds when the region changes.  The query is the same for all lanes: its position
 // comes from a lane of the tile's position register into scalar registers, the second coordinate's log / reciprocal only when it changes.
 // DS = float: the fp32-grade core's d scores; DS = u16: the bf16 d scores of the 16-bit modes (deform16_bwd_dq_kernel).
-template <typename DS>
+// MH (H / G in {1, 2} heads per offset group): head h reads its group's sample positions and the (a, c) of its output oi = h % (H / G);
+// its moments go to the global accumulators of that output (HIST [outputs][RG_RCAP][3], GRAD [outputs][RG_GRAD]), and a non-finite d
+// score sets the flag AMAX[1], which turns the parameter gradients into NaN (region_final2_mh_kernel).  Without MH, G is not read.
+template <typename DS, bool MH = false>
 __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
     const DS* __restrict__ dLT, const unsigned short* __restrict__ RID, const float* __restrict__ VS, const float* __restrict__ GQ,
     CpbParams cp, RegionView rv, const unsigned* __restrict__ AMAX, unsigned long long* __restrict__ HIST, unsigned long long* __restrict__ GRAD,
     float* __restrict__ dvs_slab, int N, int J, int H, int NST, int nkb, int nkbg, int chunks, int wpk, int tiles_per_chunk, int kbits, int shift,
-    int lcap) {
+    int lcap, int G) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   RegionBwdLds& L = *reinterpret_cast<RegionBwdLds*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, hf = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform in a scalar register: tile indices, bounds and the query positions stay scalar
   const int b = blockIdx.z, h = blockIdx.y, chunk = blockIdx.x % chunks, grp = blockIdx.x / chunks;
   const int nthreads = blockDim.x;
+  const int hpg = MH ? H / G : 1, g = MH ? h / hpg : h, oi = MH ? h - g * hpg : 0;
+  const float4* __restrict__ regs = (MH && oi) ? region_reg1(rv.hdr) : rv.reg;   // (a0, a1, c) of the head's output
+  HIST += MH ? (size_t)oi * RG_RCAP * 3 : 0;                         // the output's global accumulators
+  GRAD += MH ? (size_t)oi * RG_GRAD : 0;
   {
     const int nreg = min((int)rv.hdr->n_regions, lcap);       // lcap <= RG_LCAP: regions with LDS accumulators (tests lower it)
     for (int i = tid; i < RG_LCAP * 3; i += nthreads) L.hist[i] = 0ull;
     for (int i = tid; i < RG_GRAD; i += nthreads) L.grad[i] = 0ull;
-    for (int i = tid; i < nreg; i += nthreads) { const float4 r = rv.reg[i]; L.reg2[i] = make_float2(r.x, r.y); }
+    for (int i = tid; i < nreg; i += nthreads) { const float4 r = regs[i]; L.reg2[i] = make_float2(r.x, r.y); }
     for (int i = tid; i < CH * CH; i += nthreads) { const float w = cp.w2[i]; L.w2r[i] = w; L.w2t[(i & 31) * CH + (i >> 5)] = w; }
   }
   __syncthreads();
   const RegionScale sc = region_scale(*AMAX, kbits);
   const double Sg = __longlong_as_double(__double_as_longlong(sc.S) - ((long long)shift << 52));     // scale of the global accumulators
-  const CoopMlp mlp{cp.w1[c * 2], cp.w1[c * 2 + 1], cp.b1[c], cp.b2[c], cp.w3[c], cp.b3[0], L.w2t, L.w2r};
+  const CoopMlp mlp{cp.w1[c * 2], cp.w1[c * 2 + 1], cp.b1[c], cp.b2[c], cp.w3[oi * CH + c], cp.b3[oi], L.w2t, L.w2r};
   float big;
   asm("s_mov_b32 %0, 0x71800000" : "=s"(big));
 
@@ -1001,10 +1050,12 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
   const int key = lane * nkb + kb;
   const bool kvalid = key < J && kb < nkb;                          // (the last key group may have key blocks to spare: kb >= nkb would alias lane + 1's keys)
   const int keyc = min(key, J - 1);
-  const float vs0 = VS[((size_t)(b * H + h) * J + keyc) * 2], vs1 = VS[((size_t)(b * H + h) * J + keyc) * 2 + 1];
+  const size_t vrow = (size_t)(b * (MH ? G : H) + g) * J;            // the sample positions of the head's offset group
+  const float vs0 = VS[(vrow + keyc) * 2], vs1 = VS[(vrow + keyc) * 2 + 1];
   const int ntq = (N + QT - 1) / QT;
   const int t_begin = chunk * tiles_per_chunk, t_end = min(t_begin + tiles_per_chunk, ntq);
   float dv0 = 0.f, dv1 = 0.f;
+  unsigned bad = 0u;                                                // MH: a non-finite d score seen by this lane
   // The current run of this lane: its region, the three moment sums of d bias and the two sums of d bias * d p / d offset (d vs of a run is
   // -slope of the region * that sum: the slope is read once per run, not per pair).  cur >= RG_NONE: no run (start, pair without a region).
   unsigned cur = ~0u;
@@ -1022,7 +1073,7 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
       __hip_atomic_fetch_add(hp + 1, (unsigned long long)region_fix(r1, sc.S), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       __hip_atomic_fetch_add(hp + 2, (unsigned long long)region_fix(r2, sc.S), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     } else if (cur < (unsigned)RG_NONE) {                           // a region beyond the LDS-resident ones: global memory
-      const float4 a = rv.reg[cur];
+      const float4 a = regs[cur];
       dv0 = fmaf(-a.x, u0, dv0); dv1 = fmaf(-a.y, u1, dv1);
       glb_u64* hp = hist_g + cur * 3;
       __hip_atomic_fetch_add(hp, (unsigned long long)region_fix(r0, Sg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1086,6 +1137,11 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
         }
         const unsigned id = (ridw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
         const float dbv = dbr[q];
+        if constexpr (MH) {
+          unsigned ub = __float_as_uint(dbv);
+          asm("" : "+v"(ub));                                       // (opaque: this file is built with -fno-honor-nans)
+          bad |= ((ub & 0x7F800000u) == 0x7F800000u) ? 1u : 0u;
+        }
         if (id != cur) {                                            // the run ends: its sums go to the region's accumulators
           flush();
           if (id == RG_NONE) { nonemask |= 1u << q; cur = ~0u; }    // (the next pair starts a run whatever its id)
@@ -1142,6 +1198,9 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
     }
   }
   flush();
+  if constexpr (MH) {
+    if (__ballot(kvalid && bad != 0u) && lane == 0) atomicOr(const_cast<unsigned*>(AMAX) + 1, 1u);
+  }
   L.dvs[wave][lane] = make_float2(dv0, dv1);
   __syncthreads();
   // d vs of this chunk: the wpk waves of a key block in a fixed order -> slab [chunk][b, h][J]
@@ -1161,7 +1220,6 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
     if (v != 0ll) atomicAdd(&GRAD[i], (unsigned long long)((v + half) >> shift));
   }
 }
-
 // d vs [(b, h), J, 2] = sum of the chunk slabs in a fixed order
 __global__ __launch_bounds__(256) void region_dvs_reduce_kernel(const float2* __restrict__ slab, float2* __restrict__ dVS, size_t n, int chunks) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1253,7 +1311,130 @@ __global__ __launch_bounds__(256) void region_final2_kernel(const double* __rest
   else if (k == 1024 + 160) db3[0] = r;
 }
 
-// decisions of a pair for the parity tests: (D1, D2) of its region as two 32-bit words (tests only; pairs without a region: 0, flag)
+// ---- the same passes with one or two heads per offset group (MH kernels): per-output moments, shared layers summed over the outputs
+// d vs [(b, g), J, 2] = the chunk slabs of the group's heads, summed in a fixed order (chunks outer, heads inner)
+__global__ __launch_bounds__(256) void region_dvs_reduce_mh_kernel(const float2* __restrict__ slab, float2* __restrict__ dVS, int B, int H, int G,
+                                                                   int J, int chunks) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * G * J) return;
+  const int hpg = H / G;
+  const size_t bg = i / J, j = i - bg * J, b = bg / G, g = bg - b * G, per = (size_t)B * H * J;
+  float2 s = make_float2(0.f, 0.f);
+  for (int k = 0; k < chunks; ++k)
+    for (int o = 0; o < hpg; ++o) {
+      const float2 t = slab[(size_t)k * per + (b * H + g * hpg + o) * J + j];
+      if (k == 0 && o == 0) s = t;
+      else { s.x += t.x; s.y += t.y; }
+    }
+  dVS[i] = s;
+}
+
+// The parameter gradients from the moments M_{r,o} of every region r and output o (the formulas of region_final1_kernel with w3 row o):
+// dW2, dW1, db1, db2 are the sums over the outputs (in output order), dW3 [o] and db3 [o] per output.  Slab: dW2 [1024] | dW1 [64] |
+// db1 [32] | db2 [32] | dW3 [hpg * 32] | db3 [hpg]; with one output the layout and every operation are those of region_final1 / 2.
+constexpr int RG_HPG = 2;
+constexpr int RG_GRAD2 = 1152 + RG_HPG * (CH + 1);                  // slab of two outputs (> RG_GRAD)
+__host__ __device__ inline int region_slab_stride(int hpg) { return hpg > 1 ? RG_GRAD2 : RG_GRAD; }
+__global__ __launch_bounds__(256) void region_final1_mh_kernel(RegionTables t, const unsigned long long* __restrict__ HIST, double* __restrict__ part,
+                                                               int hpg) {
+  __shared__ double M[RG_HPG][RG_FIN][3], H1[RG_HPG][RG_FIN][CH], X2[RG_HPG][RG_FIN][CH], C1[RG_HPG][RG_FIN][CH];
+  __shared__ unsigned D1[RG_FIN], D2[RG_FIN];
+  const int tid = threadIdx.x, r0 = blockIdx.x * RG_FIN;
+  const int nreg = (int)t.hdr->n_regions;
+  const double* __restrict__ wd = t.wd;
+  for (int x = tid; x < hpg * RG_FIN * 3; x += 256) {
+    const int o = x / (RG_FIN * 3), rr = (x / 3) % RG_FIN, m = x % 3, r = r0 + rr;
+    M[o][rr][m] = r < nreg ? (double)(long long)HIST[((size_t)o * RG_RCAP + r) * 3 + m] : 0.0;
+  }
+  if (tid < RG_FIN) {
+    const int r = r0 + tid;
+    const unsigned long long k = r < nreg ? t.pat[r] : 0ull;
+    D1[tid] = (unsigned)k; D2[tid] = (unsigned)(k >> 32);
+  }
+  __syncthreads();
+  for (int x = tid; x < hpg * RG_FIN * CH; x += 256) {
+    const int o = x / (RG_FIN * CH), r = (x >> 5) % RG_FIN, i = x & 31;
+    const double x1 = wd[WD_W1 + 2 * i] * M[o][r][1] + wd[WD_W1 + 2 * i + 1] * M[o][r][2] + wd[WD_B1 + i] * M[o][r][0];
+    H1[o][r][i] = ((D1[r] >> i) & 1u) ? x1 : 0.0;
+  }
+  __syncthreads();
+  for (int x = tid; x < hpg * RG_FIN * CH; x += 256) {
+    const int o = x / (RG_FIN * CH), r = (x >> 5) % RG_FIN, q = x & 31;
+    const int w3 = o ? WD_W3B : WD_W3;
+    double v = wd[WD_B2 + q] * M[o][r][0];
+    for (int i = 0; i < CH; ++i) v = fma(wd[WD_W2 + q * CH + i], H1[o][r][i], v);
+    X2[o][r][q] = v;
+    double cc = 0.0;                                               // C1 of unit i = q
+    for (int qq = 0; qq < CH; ++qq)
+      if ((D2[r] >> qq) & 1u) cc = fma(wd[WD_W2 + qq * CH + q], wd[w3 + qq], cc);
+    C1[o][r][q] = ((D1[r] >> q) & 1u) ? cc : 0.0;
+  }
+  __syncthreads();
+  const int kw3 = 1152, kb3 = kw3 + hpg * CH, n = kb3 + hpg;
+  double* out = part + (size_t)blockIdx.x * region_slab_stride(hpg);
+  for (int k = tid; k < n; k += 256) {
+    double v = 0.0;
+    for (int o = 0; o < hpg; ++o) {
+      const int w3 = o ? WD_W3B : WD_W3;
+      double s = 0.0;
+      if (k < 1024) {
+        const int q = k >> 5, i = k & 31;
+        for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += H1[o][r][i];
+        s *= wd[w3 + q];
+      } else if (k < 1024 + 64) {
+        const int i = (k - 1024) >> 1, comp = (k - 1024) & 1;
+        for (int r = 0; r < RG_FIN; ++r) s = fma(C1[o][r][i], M[o][r][1 + comp], s);
+      } else if (k < 1024 + 96) {
+        const int i = k - 1088;
+        for (int r = 0; r < RG_FIN; ++r) s = fma(C1[o][r][i], M[o][r][0], s);
+      } else if (k < kw3) {
+        const int q = k - 1120;
+        for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += M[o][r][0];
+        s *= wd[w3 + q];
+      } else if (k < kb3) {
+        const int oo = (k - kw3) >> 5, q = (k - kw3) & 31;
+        if (oo == o)
+          for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += X2[o][r][q];
+      } else if (k - kb3 == o) {
+        for (int r = 0; r < RG_FIN; ++r) s += M[o][r][0];
+      }
+      v = o ? v + s : s;
+    }
+    out[k] = v;
+  }
+}
+// GRAD [outputs][RG_GRAD]: the direct sums of the pairs without a region, per output in the one-output layout.  FLAG != 0 (a non-finite
+// d score): every parameter gradient is NaN.
+__global__ __launch_bounds__(256) void region_final2_mh_kernel(const double* __restrict__ part, int groups, const unsigned long long* __restrict__ GRAD,
+                                                               const unsigned* __restrict__ AMAX, const unsigned* __restrict__ FLAG, int kbits_global,
+                                                               int hpg, float* __restrict__ dW1, float* __restrict__ db1, float* __restrict__ dW2,
+                                                               float* __restrict__ db2, float* __restrict__ dW3, float* __restrict__ db3) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const int kw3 = 1152, kb3 = kw3 + hpg * CH, stride = region_slab_stride(hpg);
+  if (k >= kb3 + hpg) return;
+  unsigned long long gi;
+  if (k < kw3) {
+    gi = GRAD[k];
+    for (int o = 1; o < hpg; ++o) gi += GRAD[(size_t)o * RG_GRAD + k];
+  } else if (k < kb3) {
+    gi = GRAD[(size_t)((k - kw3) >> 5) * RG_GRAD + 1152 + ((k - kw3) & 31)];
+  } else {
+    gi = GRAD[(size_t)(k - kb3) * RG_GRAD + 1184];
+  }
+  double v = (double)(long long)gi;
+  for (int g = 0; g < groups; ++g) v += part[(size_t)g * stride + k];
+  const RegionScale sc = region_scale(*AMAX, kbits_global);
+  // the quiet NaN goes out as its bit pattern: this file is built with -fno-honor-nans, under which a NaN constant may be folded away
+  const unsigned r = *FLAG ? 0x7FC00000u : __float_as_uint((float)(v / sc.S));
+  auto put = [&](float* dst, int i) { reinterpret_cast<unsigned*>(dst)[i] = r; };
+  if (k < 1024) put(dW2, k);
+  else if (k < 1024 + 64) put(dW1, k - 1024);
+  else if (k < 1024 + 96) put(db1, k - 1088);
+  else if (k < kw3) put(db2, k - 1120);
+  else if (k < kb3) put(dW3, k - kw3);
+  else put(db3, k - kb3);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side shared by the fp32-grade (deform_attn.hip) and the 16-bit (deform_attn16.hip) region entry points
 // ------------------------------------------------------------------------------------------------
@@ -1262,7 +1443,8 @@ struct RegionBwdPlan {
   int chunks, tiles_per_chunk, nkb, nkbg, ngrp, wpk, kbits, shift;
   size_t amax, hist, grad, dvs, part, total;       // byte offsets behind the dq / dkv workspace
 };
-static RegionBwdPlan region_bwd_plan(int B, int N, int J, int H) {
+// outputs: heads per offset group of an MH launch (per-output moment accumulators); 1 for every other region backward
+static RegionBwdPlan region_bwd_plan(int B, int N, int J, int H, int outputs = 1) {
   RegionBwdPlan p;
   const int ntq = (N + QT - 1) / QT;
   p.chunks = (512 + B * H - 1) / (B * H);
@@ -1285,10 +1467,10 @@ static RegionBwdPlan region_bwd_plan(int B, int N, int J, int H) {
   size_t o = (bwd_workspace(B, N, J, H).total * sizeof(float) + 255) & ~(size_t)255;
   auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
   p.amax = take(256);
-  p.hist = take((size_t)RG_RCAP * 3 * 8);
-  p.grad = take((size_t)RG_GRAD * 8);
+  p.hist = take((size_t)outputs * RG_RCAP * 3 * 8);
+  p.grad = take((size_t)outputs * RG_GRAD * 8);
   p.dvs = take((size_t)p.chunks * B * H * J * 2 * sizeof(float));
-  p.part = take((size_t)(RG_RCAP / RG_FIN) * RG_GRAD * 8);
+  p.part = take((size_t)(RG_RCAP / RG_FIN) * region_slab_stride(outputs) * 8);
   p.total = o;
   return p;
 }
@@ -1298,6 +1480,11 @@ static int check_region(const char* fn, int B, int N, int J, int H) {
   SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
   SMML_REQUIRE(J <= RG_MAX_KEYS, "%s: the region kernels take at most %d keys (got %d)", fn, RG_MAX_KEYS, J);
   return SMML_OK;
+}
+static int check_region_mh(const char* fn, int B, int N, int J, int H, int G) {
+  SMML_REQUIRE(G > 0, "%s: non-positive dimension", fn);
+  SMML_REQUIRE(H > 0 && H % G == 0 && H / G <= RG_HPG, "%s: heads (%d) must be 1 or 2 per offset group (%d groups)", fn, H, G);
+  return check_region(fn, B, N, J, H);
 }
 static int check_region_workspace(const char* fn, const void* ws, size_t bytes, const RegionBwdPlan& pl, int J) {
   if (int rc = check_workspace(fn, ws, bytes, pl.total, 256)) return rc;
@@ -1312,10 +1499,11 @@ static int region_lcap(const SmmlDeformOpts* opts) {
 
 // pass 3 of a region backward: d vs per pair, region moments (cpb_region_bwd_kernel<DS>), then the dense pass to the six parameter gradients.
 // wsb: the call's workspace (bytes), pl: its plan; amax | hist | grad were zeroed and amax filled by the dq pass of the caller.
-template <typename DS>
+// MH: the kernels of one or two heads per offset group (G groups; pl planned with H / G outputs); else G == H and one head per group.
+template <typename DS, bool MH = false>
 static int region_bias_bwd_launch(const char* fn, const DS* dlogits, const unsigned short* region_ids, const float* vs, const float* gq, CpbParams cp,
-                                  const void* tables, char* wsb, const RegionBwdPlan& pl, int B, int N, int J, int H, int nst, int lcap, float* dvs,
-                                  float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ev_start, void* ev_stop,
+                                  const void* tables, char* wsb, const RegionBwdPlan& pl, int B, int N, int J, int H, int G, int nst, int lcap,
+                                  float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ev_start, void* ev_stop,
                                   hipStream_t st) {
   const RegionTables rt = region_tables(const_cast<void*>(tables));
   const RegionView rv = region_view(const_cast<void*>(tables));
@@ -1325,23 +1513,33 @@ static int region_bias_bwd_launch(const char* fn, const DS* dlogits, const unsig
   float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
   double* part = reinterpret_cast<double*>(wsb + pl.part);
   {   // 89 KB of dynamic LDS: above the 64 KB a kernel gets without asking (a host-side attribute of the function: cheap, idempotent)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cpb_region_bwd_kernel<DS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)sizeof(RegionBwdLds));
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cpb_region_bwd_kernel<DS, MH>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RegionBwdLds));
     SMML_REQUIRE(e == hipSuccess, "%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(e));
   }
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-  hipLaunchKernelGGL(cpb_region_bwd_kernel<DS>, dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), sizeof(RegionBwdLds), st, dlogits,
+  hipLaunchKernelGGL((cpb_region_bwd_kernel<DS, MH>), dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), sizeof(RegionBwdLds), st, dlogits,
                      region_ids, vs, gq, cp, rv, amax, hist, grad, dvs_slab, N, J, H, nst, pl.nkb, pl.nkbg, pl.chunks, pl.wpk, pl.tiles_per_chunk,
-                     pl.kbits, pl.shift, lcap);
+                     pl.kbits, pl.shift, lcap, G);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
   SMML_LAUNCH_CHECK(fn);
-  const size_t n = (size_t)B * H * J;
-  hipLaunchKernelGGL(region_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(dvs_slab),
-                     reinterpret_cast<float2*>(dvs), n, pl.chunks);
   const int groups = RG_RCAP / RG_FIN;
-  hipLaunchKernelGGL(region_final1_kernel, dim3(groups), dim3(256), 0, st, rt, hist, part);
-  hipLaunchKernelGGL(region_final2_kernel, dim3((RG_GRAD + 255) / 256), dim3(256), 0, st, part, groups, grad, amax, pl.kbits - pl.shift, dw1, db1,
-                     dw2, db2, dw3, db3);
+  if (MH) {
+    const int hpg = H / G;
+    const size_t n = (size_t)B * G * J;
+    hipLaunchKernelGGL(region_dvs_reduce_mh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(dvs_slab),
+                       reinterpret_cast<float2*>(dvs), B, H, G, J, pl.chunks);
+    hipLaunchKernelGGL(region_final1_mh_kernel, dim3(groups), dim3(256), 0, st, rt, hist, part, hpg);
+    hipLaunchKernelGGL(region_final2_mh_kernel, dim3((RG_GRAD2 + 255) / 256), dim3(256), 0, st, part, groups, grad, amax, amax + 1,
+                       pl.kbits - pl.shift, hpg, dw1, db1, dw2, db2, dw3, db3);
+  } else {
+    const size_t n = (size_t)B * H * J;
+    hipLaunchKernelGGL(region_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(dvs_slab),
+                       reinterpret_cast<float2*>(dvs), n, pl.chunks);
+    hipLaunchKernelGGL(region_final1_kernel, dim3(groups), dim3(256), 0, st, rt, hist, part);
+    hipLaunchKernelGGL(region_final2_kernel, dim3((RG_GRAD + 255) / 256), dim3(256), 0, st, part, groups, grad, amax, pl.kbits - pl.shift, dw1, db1,
+                       dw2, db2, dw3, db3);
+  }
   SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }

@@ -1293,13 +1293,15 @@ int smml_cpb_regions_build(const float* w1, const float* b1, const float* w2, co
   return SMML_OK;
 }
 
-int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq,
-                                    const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                                    const float* b3, const void* tables, float* out, float* lse, float* logits_t,
-                                    unsigned short* region_ids, int B, int N, int J, int H, float scale, float dropout_p,
-                                    unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  static const char* fn = "smml_deform_attn_region_fwd_f32";
-  int rc = check_region(fn, B, N, J, H);
+}  // extern "C"
+
+// the region forward of one head per offset group (G == H) or, MH, of one or two heads per group
+template <bool MH>
+static int region_fwd_f32(const char* fn, const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables, float* out,
+                          float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G, float scale, float dropout_p,
+                          unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
+  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
   if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse, "%s: null pointer", fn);
@@ -1307,14 +1309,52 @@ int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float*
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   const RegionView rv = region_view(const_cast<void*>(tables));
-  const auto kern = region_ids ? deform_region_fwd_kernel<true> : deform_region_fwd_kernel<false>;
+  const auto kern = region_ids ? deform_region_fwd_kernel<true, float, MH> : deform_region_fwd_kernel<false, float, MH>;
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
   hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits_t, region_ids,
-                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts));
+                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts), G);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
   SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
+}
+
+template <bool MH>
+static int region_bwd_f32(const char* fn, const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables, const float* out,
+                          const float* dout, const float* lse, const float* logits_t, const unsigned short* region_ids, float* dlogits_t, float* dq,
+                          float* dk, float* dv, float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                          size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p, unsigned long long dropout_seed,
+                          void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
+  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  if (!rc) rc = check_dropout(fn, dropout_p);
+  if (rc) return rc;
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits_t && region_ids &&
+                   dlogits_t && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
+               "%s: null pointer", fn);
+  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, MH ? H / G : 1);
+  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  hipStream_t st = (hipStream_t)stream;
+  char* wsb = reinterpret_cast<char*>(workspace);
+  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);      // the accumulators of this launch: amax (| flag) | hist | grad are contiguous
+  rc = bwd_dq_dkv(fn, q, k, v, out, dout, lse, logits_t, dlogits_t, dq, dk, dv, reinterpret_cast<float*>(workspace),
+                  reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
+  if (rc) return rc;
+  // pass 3: position bias - d vs per pair, region moments, then the dense pass to the six parameter gradients
+  return region_bias_bwd_launch<float, MH>(fn, dlogits_t, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H, G,
+                                           smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+}
+
+extern "C" {
+
+int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq,
+                                    const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                                    const float* b3, const void* tables, float* out, float* lse, float* logits_t,
+                                    unsigned short* region_ids, int B, int N, int J, int H, float scale, float dropout_p,
+                                    unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
+  return region_fwd_f32<false>("smml_deform_attn_region_fwd_f32", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, lse, logits_t, region_ids,
+                               B, N, J, H, H, scale, dropout_p, dropout_seed, ev_start, ev_stop, stream, opts);
 }
 
 size_t smml_deform_attn_region_bwd_workspace_bytes(int B, int N, int J, int H) {
@@ -1329,25 +1369,50 @@ int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float*
                                     float* dv, float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
                                     void* workspace, size_t workspace_bytes, int B, int N, int J, int H, float scale, float dropout_p,
                                     unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  static const char* fn = "smml_deform_attn_region_bwd_f32";
-  int rc = check_region(fn, B, N, J, H);
-  if (!rc) rc = check_dropout(fn, dropout_p);
-  if (rc) return rc;
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits_t && region_ids &&
-                   dlogits_t && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "%s: null pointer", fn);
-  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
-  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
-  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  hipStream_t st = (hipStream_t)stream;
-  char* wsb = reinterpret_cast<char*>(workspace);
-  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);      // the accumulators of this launch: amax | hist | grad are contiguous
-  rc = bwd_dq_dkv(fn, q, k, v, out, dout, lse, logits_t, dlogits_t, dq, dk, dv, reinterpret_cast<float*>(workspace),
-                  reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
-  if (rc) return rc;
-  // pass 3: position bias - d vs per pair, region moments, then the dense pass to the six parameter gradients
-  return region_bias_bwd_launch<float>(fn, dlogits_t, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H,
-                                       smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+  return region_bwd_f32<false>("smml_deform_attn_region_bwd_f32", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, dout, lse, logits_t,
+                               region_ids, dlogits_t, dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3, workspace, workspace_bytes, B, N, J, H, H, scale,
+                               dropout_p, dropout_seed, ev_start, ev_stop, stream, opts);
+}
+
+// ---- one or two heads per offset group (H / G in {1, 2}): the tables carry the (a, c) of every output of the MLP; head h takes output
+// h % (H / G) and the sample positions of group h / (H / G)
+int smml_cpb_regions_mh_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int outputs,
+                              float pmax, void* tables, size_t tables_bytes, void* stream) {
+  static const char* fn = "smml_cpb_regions_mh_build";
+  SMML_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && tables, "%s: null pointer", fn);
+  SMML_REQUIRE(outputs == 1 || outputs == 2, "%s: outputs (heads per offset group) must be 1 or 2 (got %d)", fn, outputs);
+  SMML_REQUIRE(pmax > 0.f && pmax < 16.f, "%s: pmax must be in (0, 16) (got %g)", fn, (double)pmax);
+  SMML_REQUIRE(tables_bytes >= region_layout().total, "%s: table buffer too small (%zu < %zu)", fn, tables_bytes, region_layout().total);
+  SMML_REQUIRE((reinterpret_cast<size_t>(tables) & 255) == 0, "%s: table buffer must be 256-byte aligned", fn);
+  region_build_launch(CpbParams{w1, b1, w2, b2, w3, b3}, pmax, tables, (hipStream_t)stream, outputs);
+  SMML_LAUNCH_CHECK(fn);
+  return SMML_OK;
+}
+
+int smml_deform_attn_region_mh_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                       float* out, float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                       float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream,
+                                       const SmmlDeformOpts* opts) {
+  return region_fwd_f32<true>("smml_deform_attn_region_mh_fwd_f32", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, lse, logits_t, region_ids,
+                              B, N, J, H, G, scale, dropout_p, dropout_seed, ev_start, ev_stop, stream, opts);
+}
+
+size_t smml_deform_attn_region_mh_bwd_workspace_bytes(int B, int N, int J, int H, int G) {
+  if (B <= 0 || N <= 0 || J <= 0 || H <= 0 || G <= 0 || H % G || H / G > RG_HPG || !deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS) return 0;
+  return region_bwd_plan(B, N, J, H, H / G).total;
+}
+
+int smml_deform_attn_region_mh_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                       const float* out, const float* dout, const float* lse, const float* logits_t,
+                                       const unsigned short* region_ids, float* dlogits_t, float* dq, float* dk, float* dv, float* dvs, float* dw1,
+                                       float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B,
+                                       int N, int J, int H, int G, float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start,
+                                       void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
+  return region_bwd_f32<true>("smml_deform_attn_region_mh_bwd_f32", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, dout, lse, logits_t,
+                              region_ids, dlogits_t, dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3, workspace, workspace_bytes, B, N, J, H, G, scale,
+                              dropout_p, dropout_seed, ev_start, ev_stop, stream, opts);
 }
 
 // ------------------------------------------------------------------------------------------------

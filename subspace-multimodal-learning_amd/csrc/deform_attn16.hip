@@ -1501,13 +1501,16 @@ int smml_deform_attn16_bwd(const float* q, const float* k, const float* v, const
 
 // ---- position bias per linear region (cpb_regions.h) in the 16-bit compute modes: the bias is the fp32 lookup of the fp32-grade path, the
 // attention core runs on single-term T operands with fp16 scores / bf16 d scores (2-D signed-log offsets, one head per offset group)
-int smml_deform_attn16_region_fwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
-                                  const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
-                                  float* out, float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H,
-                                  float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop,
-                                  void* stream, const SmmlDeformOpts* opts) {
-  static const char* fn = "smml_deform_attn16_region_fwd";
-  int rc = check_region(fn, B, N, J, H);
+}  // extern "C"
+
+// the 16-bit region forward of one head per offset group (G == H) or, MH, of one or two heads per group
+template <bool MH>
+static int region16_fwd(const char* fn, const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                        const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables, float* out,
+                        float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H, int G, float scale,
+                        float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
+                        const SmmlDeformOpts* opts) {
+  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
   if (rc) return rc;
   SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
   if ((rc = check_dropout(fn, dropout_p))) return rc;
@@ -1516,15 +1519,55 @@ int smml_deform_attn16_region_fwd(const float* q, const float* k, const float* v
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   CpbParams cp{w1, b1, w2, b2, w3, b3};
   const RegionView rv = region_view(const_cast<void*>(tables));
-  const auto kern = dtype == 1 ? (region_ids ? deform_region_fwd_kernel<true, _Float16> : deform_region_fwd_kernel<false, _Float16>)
-                               : (region_ids ? deform_region_fwd_kernel<true, __bf16> : deform_region_fwd_kernel<false, __bf16>);
+  const auto kern = dtype == 1 ? (region_ids ? deform_region_fwd_kernel<true, _Float16, MH> : deform_region_fwd_kernel<false, _Float16, MH>)
+                               : (region_ids ? deform_region_fwd_kernel<true, __bf16, MH> : deform_region_fwd_kernel<false, __bf16, MH>);
   hipStream_t st = (hipStream_t)stream;
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
   hipLaunchKernelGGL(kern, dim3((N + QT * WAVES - 1) / (QT * WAVES), H, B), dim3(256), 0, st, q, k, v, vs, gq, cp, rv, out, lse, logits16, region_ids,
-                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts));
+                     N, J, H, smml_deform_attn_nst(N), scale, dc, region_lcap(opts), G);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
   SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
+}
+
+template <bool MH>
+static int region16_bwd(const char* fn, const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                        const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables, const float* out,
+                        const float* dout, const float* lse, const unsigned short* logits16, const unsigned short* region_ids,
+                        unsigned short* dlogits16, float* dq, float* dk, float* dv, float* dvs, float* dw1, float* db1, float* dw2, float* db2,
+                        float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B, int N, int J, int H, int G, float scale,
+                        float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
+                        const SmmlDeformOpts* opts) {
+  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  if (rc) return rc;
+  SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
+  if ((rc = check_dropout(fn, dropout_p))) return rc;
+  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits16 && region_ids &&
+                   dlogits16 && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
+               "%s: null pointer", fn);
+  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, MH ? H / G : 1);
+  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
+  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
+  hipStream_t st = (hipStream_t)stream;
+  char* wsb = reinterpret_cast<char*>(workspace);
+  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);        // amax (| flag) | hist | grad are contiguous
+  rc = bwd16_dq_dkv(fn, dtype, q, k, v, out, dout, lse, logits16, dlogits16, dq, dk, dv, reinterpret_cast<float*>(workspace),
+                    reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
+  if (rc) return rc;
+  // pass 3: position bias per region on the bf16 d scores
+  return region_bias_bwd_launch<u16, MH>(fn, dlogits16, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H, G,
+                                         smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+}
+
+extern "C" {
+
+int smml_deform_attn16_region_fwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                  const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                  float* out, float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H,
+                                  float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop,
+                                  void* stream, const SmmlDeformOpts* opts) {
+  return region16_fwd<false>("smml_deform_attn16_region_fwd", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, lse, logits16, region_ids, B, N,
+                             J, H, H, scale, dropout_p, dropout_seed, dtype, ev_start, ev_stop, stream, opts);
 }
 
 /* workspace: smml_deform_attn_region_bwd_workspace_bytes (the fp32-grade region backward's), 256-byte aligned */
@@ -1536,26 +1579,33 @@ int smml_deform_attn16_region_bwd(const float* q, const float* k, const float* v
                                   size_t workspace_bytes, int B, int N, int J, int H, float scale, float dropout_p,
                                   unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
                                   const SmmlDeformOpts* opts) {
-  static const char* fn = "smml_deform_attn16_region_bwd";
-  int rc = check_region(fn, B, N, J, H);
-  if (rc) return rc;
-  SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
-  if ((rc = check_dropout(fn, dropout_p))) return rc;
-  SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits16 && region_ids &&
-                   dlogits16 && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
-               "%s: null pointer", fn);
-  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H);
-  if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
-  const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
-  hipStream_t st = (hipStream_t)stream;
-  char* wsb = reinterpret_cast<char*>(workspace);
-  (void)hipMemsetAsync(wsb + pl.amax, 0, pl.dvs - pl.amax, st);        // amax | hist | grad are contiguous
-  rc = bwd16_dq_dkv(fn, dtype, q, k, v, out, dout, lse, logits16, dlogits16, dq, dk, dv, reinterpret_cast<float*>(workspace),
-                    reinterpret_cast<unsigned*>(wsb + pl.amax), B, N, J, H, scale, dc, st);
-  if (rc) return rc;
-  // pass 3: position bias per region on the bf16 d scores
-  return region_bias_bwd_launch<u16>(fn, dlogits16, region_ids, vs, gq, CpbParams{w1, b1, w2, b2, w3, b3}, tables, wsb, pl, B, N, J, H,
-                                     smml_deform_attn_nst(N), region_lcap(opts), dvs, dw1, db1, dw2, db2, dw3, db3, ev_start, ev_stop, st);
+  return region16_bwd<false>("smml_deform_attn16_region_bwd", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, dout, lse, logits16, region_ids,
+                             dlogits16, dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3, workspace, workspace_bytes, B, N, J, H, H, scale, dropout_p,
+                             dropout_seed, dtype, ev_start, ev_stop, stream, opts);
+}
+
+/* one or two heads per offset group: tables from smml_cpb_regions_mh_build with outputs = H / G; workspace:
+   smml_deform_attn_region_mh_bwd_workspace_bytes, 256-byte aligned */
+int smml_deform_attn16_region_mh_fwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                     const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                     float* out, float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H, int G,
+                                     float scale, float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop,
+                                     void* stream, const SmmlDeformOpts* opts) {
+  return region16_fwd<true>("smml_deform_attn16_region_mh_fwd", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, lse, logits16, region_ids, B,
+                            N, J, H, G, scale, dropout_p, dropout_seed, dtype, ev_start, ev_stop, stream, opts);
+}
+
+int smml_deform_attn16_region_mh_bwd(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                     const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables,
+                                     const float* out, const float* dout, const float* lse, const unsigned short* logits16,
+                                     const unsigned short* region_ids, unsigned short* dlogits16, float* dq, float* dk, float* dv, float* dvs,
+                                     float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                                     size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p,
+                                     unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
+                                     const SmmlDeformOpts* opts) {
+  return region16_bwd<true>("smml_deform_attn16_region_mh_bwd", q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, tables, out, dout, lse, logits16, region_ids,
+                            dlogits16, dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3, workspace, workspace_bytes, B, N, J, H, G, scale, dropout_p,
+                            dropout_seed, dtype, ev_start, ev_stop, stream, opts);
 }
 
 // mask table of the table-forward backward (include/smml.h): cells per axis, and the kernel that fills one

@@ -102,9 +102,14 @@ class DeformCrossAttention2D(nn.Module):
     def __init__(self, *, dim, dim_head=64, heads=8, dropout=0., downsample_factor=4, offset_scale=4,
                  offset_groups=8, offset_kernel_size=6, group_queries=True, group_key_values=True,
                  grid_hw: Optional[Tuple[int, int]] = None, consistent_grid_norm: bool = False, compute_dtype=None,
-                 cpb_table: bool = False):
+                 cpb_table: bool = False, cpb_regions_multi_head: bool = False):
         super().__init__()
         self.consistent_grid_norm = bool(consistent_grid_norm)
+        # cpb_regions_multi_head (off by default): the position bias per linear region of its MLP also with two heads per offset group
+        # (functional.deform_attention; one head per group takes that path anyway).  No table mode; other limits are checked at the call
+        if cpb_regions_multi_head and cpb_table:
+            raise ValueError("cpb_regions_multi_head (the region path) and cpb_table exclude each other")
+        self.cpb_regions_multi_head = bool(cpb_regions_multi_head)
         Fh._dtype16(compute_dtype)             # validates: None | 'bf16' | 'fp16'
         self.compute_dtype = compute_dtype     # additive: None = the fp32-grade path, else the 16-bit compute mode of the fused core
         if cpb_table and compute_dtype is None:
@@ -168,7 +173,8 @@ class DeformCrossAttention2D(nn.Module):
                 * L.smml_offsets_out_len(Ww, self.offset_kernel_size, self.downsample_factor))
         w = self.rel_pos_bias.tensors()
         return Fh.deform_path(posdim=2, heads=self.heads, groups=self.offset_groups, keys=keys, w2_shape=w[2].shape, w3_shape=w[4].shape,
-                              compute_dtype=self.compute_dtype, cpb_table=self.cpb_table, region_pmax_given=True) == "region"
+                              compute_dtype=self.compute_dtype, cpb_table=self.cpb_table, region_pmax_given=True,
+                              regions_multi_head=self.cpb_regions_multi_head) == "region"
 
     def prefetch_regions(self, n_tokens: int) -> None:
         """Starts the build of the position bias's region tables on a side stream (functional.RegionPrefetch); the next forward_tokens on
@@ -213,6 +219,8 @@ class DeformCrossAttention2D(nn.Module):
         if self.cpb_table:
             tab = {"cpb_table": self.cpb_table, "cpb_table_pmax": None if self.consistent_grid_norm else Fh.table_pmax(gqb, vsb),   # None: from the data
                    "cpb_table_grid": (Hh, Ww)}                 # gq is a regular grid in both normalisations
+        if self.cpb_regions_multi_head:
+            tab["cpb_regions_multi_head"] = True
         o = Fh.deform_attention(q, k, v, vs, gq, *self.rel_pos_bias.tensors(), heads=H, groups=G, scale=self.scale,
                                 compute_dtype=self.compute_dtype, fork=fork, **tab, **_dropout_args(self, q.device))
         # the output projection follows the core's compute mode (single-term 16-bit operands, fp32 accumulation and storage)

@@ -872,6 +872,7 @@ REGION_LDS_CAP = 0           # tests: regions with an id >= this take the global
 
 REGION_GRID, REGION_SUB, REGION_SUBCAP, REGION_EDGES, REGION_RCAP = 1024, 8, 16384, 1 << 15, 4096     # csrc/cpb_regions.h
 REGION_CODE_SUB0, REGION_CODE_EDGE0 = 4096, 4096 + 16384
+REGION_HASH, REGION_CANDCAP, REGION_WD = 16384, 1 << 18, 1232                                         # csrc/cpb_regions.h (build scratch)
 
 
 def _blocks(tables: torch.Tensor, *sizes):
@@ -885,10 +886,16 @@ def _blocks(tables: torch.Tensor, *sizes):
 
 def region_tables_view(tables: torch.Tensor):
     """Views into a region-table buffer (tests / diagnostics; layout: region_layout() of csrc/cpb_regions.h): header counters,
-    (a0, a1, c) per region, ReLU patterns (D1 | D2 << 32), 16-bit codes of the cells and sub-cells, single-kink records by slot."""
+    (a0, a1, c) per region, ReLU patterns (D1 | D2 << 32), 16-bit codes of the cells and sub-cells, single-kink records by slot, and
+    "reg1": the (a0, a1, c) of the MLP's second output (tables of two heads per offset group, smml_cpb_regions_mh_build)."""
     G, SUB = REGION_GRID, REGION_SUB
-    hdr, reg, pat, t0, t1, edge = _blocks(tables, 256, REGION_RCAP * 16, REGION_RCAP * 8, G * G * 2, REGION_SUBCAP * SUB * SUB * 2,
-                                          REGION_EDGES * 16)
+    blocks = _blocks(tables, 256, REGION_RCAP * 16, REGION_RCAP * 8, G * G * 2, REGION_SUBCAP * SUB * SUB * 2, REGION_EDGES * 16,
+                     # build scratch: t0, t1, ekey, hkey, hid, sublist, cand, klist, corners, subcorners, wd; then the second output's (a, c)
+                     G * G * 4, REGION_SUBCAP * SUB * SUB * 4, REGION_EDGES * 4, REGION_HASH * 8, REGION_HASH * 4, REGION_SUBCAP * 4,
+                     REGION_CANDCAP * 8, REGION_HASH * 12, (G + 1) ** 2 * 8, REGION_SUBCAP * (SUB + 1) ** 2 * 8, REGION_WD * 8,
+                     REGION_RCAP * 16)
+    hdr, reg, pat, t0, t1, edge = blocks[:6]
+    reg1 = blocks[-1]
     hdr = hdr.view(torch.int32)
     n_sub, n_edge, n_regions = int(hdr[0]), int(hdr[1]), int(hdr[3])
     return {"n_sub": n_sub, "n_edge": n_edge, "n_cand": int(hdr[2]), "n_regions": n_regions, "n_keys": int(hdr[4]), "overflow": int(hdr[5]),
@@ -898,7 +905,8 @@ def region_tables_view(tables: torch.Tensor):
             "pat": pat.view(torch.int64)[:n_regions],
             "t0": t0.view(torch.int16).view(G, G),
             "t1": t1.view(torch.int16).view(REGION_SUBCAP, SUB * SUB)[:max(min(n_sub, REGION_SUBCAP), 1)],
-            "edge": edge.view(torch.float32).view(REGION_EDGES, 4)}
+            "edge": edge.view(torch.float32).view(REGION_EDGES, 4),
+            "reg1": reg1.view(torch.float32).view(REGION_RCAP, 4)[:n_regions]}
 
 
 def region_patterns(region_ids: torch.Tensor, tables: torch.Tensor):
@@ -914,13 +922,17 @@ def region_patterns(region_ids: torch.Tensor, tables: torch.Tensor):
 
 def cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax: float, tables: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The region tables of the position-bias MLP with these parameters over [-pmax, pmax]^2 (uint8 scratch owned by the caller), built
-    on the current stream."""
+    on the current stream.  w3 [outputs, 32] with outputs = heads per offset group: a second output adds its (a, c) (one buffer size
+    for both)."""
     L = capi.lib()
     nbytes = L.smml_cpb_regions_bytes()
     if tables is None:
         tables = torch.empty(nbytes, device=w1.device, dtype=torch.uint8)
-    capi.check(L.smml_cpb_regions_build(capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.fptr(_c(w2)), capi.fptr(_c(b2)), capi.fptr(_c(w3)),
-                                        capi.fptr(_c(b3)), float(pmax), capi.ptr(tables), nbytes, capi.stream()), "cpb_regions_build")
+    w = (capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.fptr(_c(w2)), capi.fptr(_c(b2)), capi.fptr(_c(w3)), capi.fptr(_c(b3)))
+    if w3.shape[0] == 1:
+        capi.check(L.smml_cpb_regions_build(*w, float(pmax), capi.ptr(tables), nbytes, capi.stream()), "cpb_regions_build")
+    else:
+        capi.check(L.smml_cpb_regions_mh_build(*w, int(w3.shape[0]), float(pmax), capi.ptr(tables), nbytes, capi.stream()), "cpb_regions_mh_build")
     return tables
 
 
@@ -982,12 +994,34 @@ def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtyp
     return _region1d_why(vs.shape[-1], k.shape[1], w2.shape, w3.shape, heads, groups, compute_dtype, cpb_table, log_distance)
 
 
+def _region_mh_why(keys: int, w2_shape, w3_shape, heads: int, groups: int, cpb_table, cpb_regions, log_distance: bool, region_pmax_given: bool,
+                   capturing: bool):
+    if not log_distance:
+        return "raw distances (cpb_log_distance=False)"
+    if cpb_table:
+        return "the table modes"
+    if cpb_regions is not None and not bool(cpb_regions):
+        return "cpb_regions=False (the per-pair kernels)"
+    if groups <= 0 or heads % groups or heads // groups not in (1, 2):
+        return f"heads // groups = {heads // groups if groups > 0 else 0} (supported: 1, 2)"
+    if keys > REGION_MAX_KEYS:
+        return f"{keys} keys (at most {REGION_MAX_KEYS})"
+    if tuple(w2_shape) != (32, 32) or tuple(w3_shape) != (heads // groups, 32):
+        return "a bias MLP other than 2 -> 32 -> 32 -> heads // groups"
+    if capturing and not region_pmax_given:
+        return "a hipGraph capture without cpb_region_pmax (its pmax would come from the data: a host sync)"
+    return None
+
+
 def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32, 32), w3_shape=(1, 32), log_distance: bool = True,
-                compute_dtype=None, cpb_table=False, cpb_regions=None, region_pmax_given: bool = False, capturing: bool = False) -> str:
+                compute_dtype=None, cpb_table=False, cpb_regions=None, region_pmax_given: bool = False, capturing: bool = False,
+                regions_multi_head: bool = False) -> str:
     """The core a deform_attention call with these shapes and options takes: 'region1d' (the 1-D position bias per linear piece), 'table',
     'pair_table_forward' (per-pair backward of a table forward), 'region' (2-D, per linear region; fp32-grade or 16-bit core) or 'pair'
     (the per-pair MLP; fp32-grade or 16-bit core).  Raises on a combination no core supports.  No GPU work; the module switches
-    (CPB_REGIONS) are read at call time.  capturing: the call is being captured in a hipGraph (a 2-D region call then needs its pmax)."""
+    (CPB_REGIONS) are read at call time.  capturing: the call is being captured in a hipGraph (a 2-D region call then needs its pmax).
+    regions_multi_head (2-D positions): the region path on request for one or two heads per offset group, in either compute mode; any
+    combination it does not support raises ValueError (never a silent fall-back).  Without it the rules above are unchanged."""
     if cpb_table not in (False, True, None, "forward", "full"):
         raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
     if cpb_regions is not None and bool(cpb_regions) and posdim == 1:
@@ -996,6 +1030,12 @@ def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32
         if why is not None:
             raise ValueError(f"cpb_regions=True with 1-D positions: the piece path does not support {why}")
         return "region1d"
+    if regions_multi_head and posdim == 2:
+        _dtype16(compute_dtype)
+        why = _region_mh_why(keys, w2_shape, w3_shape, heads, groups, cpb_table, cpb_regions, log_distance, region_pmax_given, capturing)
+        if why is not None:
+            raise ValueError(f"cpb_regions_multi_head=True: the 2-D region path does not support {why}")
+        return "region"
     m16 = _dtype16(compute_dtype)
     if cpb_table:
         if not log_distance:
@@ -1053,12 +1093,14 @@ def _grads(ctx, *grads):
 class _DeformAttnRegion(torch.autograd.Function):
     """The fused core with the position bias per linear region of its MLP (include/smml.h): 2-D (csrc/cpb_regions.h; fp32-grade or, with
     compute_dtype, the 16-bit core) or 1-D per linear piece (csrc/cpb_regions1d.h; fp32-grade core).  pmax: half-width of the tables'
-    square (2-D) / index grid (1-D; None: the span of the breakpoints); prefetch: a RegionPrefetch of the 2-D tables, if any."""
+    square (2-D) / index grid (1-D; None: the span of the breakpoints); prefetch: a RegionPrefetch of the 2-D tables, if any.
+    multi_head (2-D): the entry points of one or two heads per offset group (include/smml.h, "_mh")."""
 
     @staticmethod
     def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
-                pmax, prefetch):
+                pmax, prefetch, multi_head=False):
         ctx.fork, ctx.seed_offset = fork, seed_offset
+        ctx.multi_head = bool(multi_head)
         q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
         B, N, _ = q.shape
         J = k.shape[1]
@@ -1087,9 +1129,15 @@ class _DeformAttnRegion(torch.autograd.Function):
         else:
             ropts = capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)
             w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
-            fn, ev, name, dt = ((L.smml_deform_attn_region_fwd_f32, "deform_region_fwd", "deform_attn_region_fwd", ()) if m16 is None else
-                                (L.smml_deform_attn16_region_fwd, "deform16_region_fwd", "deform_attn16_region_fwd", (m16[0],)))
-            capi.check(fn(*qkv, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), B, N, J, heads, float(scale),
+            if ctx.multi_head:
+                fn, ev, name, dt = ((L.smml_deform_attn_region_mh_fwd_f32, "deform_region_mh_fwd", "deform_attn_region_mh_fwd", ()) if m16 is None
+                                    else (L.smml_deform_attn16_region_mh_fwd, "deform16_region_mh_fwd", "deform_attn16_region_mh_fwd", (m16[0],)))
+                hg = (heads, groups)
+            else:
+                fn, ev, name, dt = ((L.smml_deform_attn_region_fwd_f32, "deform_region_fwd", "deform_attn_region_fwd", ()) if m16 is None else
+                                    (L.smml_deform_attn16_region_fwd, "deform16_region_fwd", "deform_attn16_region_fwd", (m16[0],)))
+                hg = (heads,)
+            capi.check(fn(*qkv, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), B, N, J, *hg, float(scale),
                           float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), ropts), name)
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
@@ -1123,13 +1171,20 @@ class _DeformAttnRegion(torch.autograd.Function):
                 *grads, capi.ptr(ws), wsb, B, N, J, heads, groups, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region1d_bwd", pairs),
                 capi.stream(), capi.deform_opts(ctx.seed_offset)), "deform_attn_region1d_bwd")
             return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
-        wsb = L.smml_deform_attn_region_bwd_workspace_bytes(B, N, J, heads)
+        if ctx.multi_head:
+            hg = (heads, groups)
+            wsb = L.smml_deform_attn_region_mh_bwd_workspace_bytes(B, N, J, heads, groups)
+            fn, ev, name, dt = ((L.smml_deform_attn_region_mh_bwd_f32, "cpb_region_mh_bwd", "deform_attn_region_mh_bwd", ()) if m16 is None else
+                                (L.smml_deform_attn16_region_mh_bwd, "cpb16_region_mh_bwd", "deform_attn16_region_mh_bwd", (m16[0],)))
+        else:
+            hg = (heads,)
+            wsb = L.smml_deform_attn_region_bwd_workspace_bytes(B, N, J, heads)
+            fn, ev, name, dt = ((L.smml_deform_attn_region_bwd_f32, "cpb_region_bwd", "deform_attn_region_bwd", ()) if m16 is None else
+                                (L.smml_deform_attn16_region_bwd, "cpb16_region_bwd", "deform_attn16_region_bwd", (m16[0],)))
         ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
         w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
-        fn, ev, name, dt = ((L.smml_deform_attn_region_bwd_f32, "cpb_region_bwd", "deform_attn_region_bwd", ()) if m16 is None else
-                            (L.smml_deform_attn16_region_bwd, "cpb16_region_bwd", "deform_attn16_region_bwd", (m16[0],)))
         capi.check(fn(*fwd, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits),
-                      *grads, capi.ptr(ws), wsb, B, N, J, heads, scale, dropout_p, dropout_seed, *dt, *TIMER.events(ev, pairs), capi.stream(),
+                      *grads, capi.ptr(ws), wsb, B, N, J, *hg, scale, dropout_p, dropout_seed, *dt, *TIMER.events(ev, pairs), capi.stream(),
                       capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
         return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
@@ -1380,7 +1435,7 @@ def graph_seed_offset(device, allocate_only: bool = False):
 def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, groups: int, scale: float,
                      dropout_p: float = 0.0, dropout_seed: int = 0, dropout_seed_offset=None, compute_dtype=None, fork=None,
                      cpb_table: bool = False, cpb_table_pmax=None, cpb_table_grid=None, log_distance: bool = True,
-                     cpb_regions=None, cpb_region_pmax=None, cpb_region_prefetch=None):
+                     cpb_regions=None, cpb_region_pmax=None, cpb_region_prefetch=None, cpb_regions_multi_head: bool = False):
     """dropout(softmax(scale q k^T + CPB(gq - vs))) v.  q [B, N, H*64], k/v [B, J, H*64], vs [(B G), J, P], gq [N, P].
     dropout_p > 0 applies nn.Dropout semantics to the probabilities with a counter-based mask from dropout_seed
     (+ the value of the device tensor dropout_seed_offset at run time, see graph_seed_offset).
@@ -1395,17 +1450,21 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
     builds d table on the matrix pipe instead of with LDS atomics.
     cpb_regions True with 1-D positions: the position bias per linear piece of its MLP (csrc/cpb_regions1d.h; signed-log offsets, the
     fp32-grade core, heads // groups in {1, 2}; anything else raises), cpb_region_pmax = half-width of its index grid (None: the span of
-    the breakpoints; no host sync either way)."""
+    the breakpoints; no host sync either way).
+    cpb_regions_multi_head True with 2-D positions: the position bias per linear region also for two heads per offset group (w3 [2, 32];
+    include/smml.h "_mh" entry points; signed-log offsets, either compute mode, no table mode; anything else raises)."""
+    mh = bool(cpb_regions_multi_head) and vs.shape[-1] == 2
     path = deform_path(posdim=vs.shape[-1], heads=heads, groups=groups, keys=k.shape[1], w2_shape=w2.shape, w3_shape=w3.shape,
                        log_distance=log_distance, compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions,
                        region_pmax_given=cpb_region_pmax is not None,
-                       capturing=cpb_region_pmax is None and q.is_cuda and torch.cuda.is_current_stream_capturing())
+                       capturing=cpb_region_pmax is None and q.is_cuda and torch.cuda.is_current_stream_capturing(),
+                       regions_multi_head=mh)
     if path in ("region", "region1d"):
         pmax = cpb_region_pmax
         if path == "region" and pmax is None:      # from the data: one host sync
             pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
         return _DeformAttnRegion.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None)
+                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None, mh)
     if path == "pair":
         return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
                                      dropout_seed_offset, compute_dtype, fork, None, log_distance)
