@@ -1014,7 +1014,7 @@ struct RegionBwdLds {                    // dynamic LDS of cpb_region_bwd_kernel
 // DS = float: the fp32-grade core's d scores; DS = u16: the bf16 d scores of the 16-bit modes (deform16_bwd_dq_kernel).
 // MH (H / G in {1, 2} heads per offset group): head h reads its group's sample positions and the (a, c) of its output oi = h % (H / G);
 // its moments go to the global accumulators of that output (HIST [outputs][RG_RCAP][3], GRAD [outputs][RG_GRAD]), and a non-finite d
-// score sets the flag AMAX[1], which turns the parameter gradients into NaN (region_final2_mh_kernel).  Without MH, G is not read.
+// score sets the flag AMAX[1], which turns the parameter gradients into NaN (region_final2_kernel).  Without MH, G is not read.
 template <typename DS, bool MH = false>
 __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
     const DS* __restrict__ dLT, const unsigned short* __restrict__ RID, const float* __restrict__ VS, const float* __restrict__ GQ,
@@ -1220,131 +1220,73 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
     if (v != 0ll) atomicAdd(&GRAD[i], (unsigned long long)((v + half) >> shift));
   }
 }
-// d vs [(b, h), J, 2] = sum of the chunk slabs in a fixed order
-__global__ __launch_bounds__(256) void region_dvs_reduce_kernel(const float2* __restrict__ slab, float2* __restrict__ dVS, size_t n, int chunks) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float2 s = slab[i];
-  for (int k = 1; k < chunks; ++k) { const float2 t = slab[(size_t)k * n + i]; s.x += t.x; s.y += t.y; }
-  dVS[i] = s;
-}
-
-// The six parameter gradients from the region moments M_r = sum d bias (1, p0, p1) - all of them are linear in M:
-//   X1_i = W1[i] . (M1, M2) + b1_i M0,  H1_i = d1_i X1_i;   X2_o = W2[o] . H1 + b2_o M0;   G2_o = d2_o w3_o;   C1_i = d1_i sum_o W2[o][i] G2_o
-//   dW3_o += d2_o X2_o;  db3 += M0;  db2_o += G2_o M0;  dW2[o][i] += G2_o H1_i;  db1_i += C1_i M0;  dW1[i] += C1_i (M1, M2)
-// Stage 1: one workgroup per 32 regions -> partial sums [groups][RG_GRAD] (fp64); stage 2 adds the groups in order.
-constexpr int RG_FIN = 32;
-__global__ __launch_bounds__(256) void region_final1_kernel(RegionTables t, const unsigned long long* __restrict__ HIST, double* __restrict__ part) {
-  __shared__ double M[RG_FIN][3], H1[RG_FIN][CH], X2[RG_FIN][CH], C1[RG_FIN][CH];
-  __shared__ unsigned D1[RG_FIN], D2[RG_FIN];
-  const int tid = threadIdx.x, r0 = blockIdx.x * RG_FIN;
-  const int nreg = (int)t.hdr->n_regions;
-  const double* __restrict__ wd = t.wd;
-  if (tid < RG_FIN * 3) {
-    const int r = r0 + tid / 3;
-    M[tid / 3][tid % 3] = r < nreg ? (double)(long long)HIST[(size_t)r * 3 + tid % 3] : 0.0;
-  }
-  if (tid < RG_FIN) {
-    const int r = r0 + tid;
-    const unsigned long long k = r < nreg ? t.pat[r] : 0ull;
-    D1[tid] = (unsigned)k; D2[tid] = (unsigned)(k >> 32);
-  }
-  __syncthreads();
-  for (int x = tid; x < RG_FIN * CH; x += 256) {
-    const int r = x >> 5, i = x & 31;
-    const double x1 = wd[WD_W1 + 2 * i] * M[r][1] + wd[WD_W1 + 2 * i + 1] * M[r][2] + wd[WD_B1 + i] * M[r][0];
-    H1[r][i] = ((D1[r] >> i) & 1u) ? x1 : 0.0;
-  }
-  __syncthreads();
-  for (int x = tid; x < RG_FIN * CH; x += 256) {
-    const int r = x >> 5, o = x & 31;
-    double v = wd[WD_B2 + o] * M[r][0];
-    for (int i = 0; i < CH; ++i) v = fma(wd[WD_W2 + o * CH + i], H1[r][i], v);
-    X2[r][o] = v;
-    double cc = 0.0;                                               // C1 of unit i = o
-    for (int oo = 0; oo < CH; ++oo)
-      if ((D2[r] >> oo) & 1u) cc = fma(wd[WD_W2 + oo * CH + o], wd[WD_W3 + oo], cc);
-    C1[r][o] = ((D1[r] >> o) & 1u) ? cc : 0.0;
-  }
-  __syncthreads();
-  double* out = part + (size_t)blockIdx.x * RG_GRAD;
-  for (int k = tid; k < RG_GRAD; k += 256) {
-    double v = 0.0;
-    if (k < 1024) {
-      const int o = k >> 5, i = k & 31;
-      for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> o) & 1u) v += H1[r][i];
-      v *= wd[WD_W3 + o];
-    } else if (k < 1024 + 64) {
-      const int i = (k - 1024) >> 1, comp = (k - 1024) & 1;
-      for (int r = 0; r < RG_FIN; ++r) v = fma(C1[r][i], M[r][1 + comp], v);
-    } else if (k < 1024 + 96) {
-      const int i = k - 1088;
-      for (int r = 0; r < RG_FIN; ++r) v = fma(C1[r][i], M[r][0], v);
-    } else if (k < 1024 + 128) {
-      const int o = k - 1120;
-      for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> o) & 1u) v += M[r][0];
-      v *= wd[WD_W3 + o];
-    } else if (k < 1024 + 160) {
-      const int o = k - 1152;
-      for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> o) & 1u) v += X2[r][o];
-    } else if (k == 1024 + 160) {
-      for (int r = 0; r < RG_FIN; ++r) v += M[r][0];
-    }
-    out[k] = v;
-  }
-}
-__global__ __launch_bounds__(256) void region_final2_kernel(const double* __restrict__ part, int groups, const unsigned long long* __restrict__ GRAD,
-                                                            const unsigned* __restrict__ AMAX, int kbits_global, float* __restrict__ dW1,
-                                                            float* __restrict__ db1, float* __restrict__ dW2, float* __restrict__ db2,
-                                                            float* __restrict__ dW3, float* __restrict__ db3) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= RG_GRAD) return;
-  double v = (double)(long long)GRAD[k];
-  for (int g = 0; g < groups; ++g) v += part[(size_t)g * RG_GRAD + k];
-  const RegionScale sc = region_scale(*AMAX, kbits_global);
-  const float r = (float)(v / sc.S);
-  if (k < 1024) dW2[k] = r;
-  else if (k < 1024 + 64) dW1[k - 1024] = r;
-  else if (k < 1024 + 96) db1[k - 1088] = r;
-  else if (k < 1024 + 128) db2[k - 1120] = r;
-  else if (k < 1024 + 160) dW3[k - 1152] = r;
-  else if (k == 1024 + 160) db3[0] = r;
-}
-
-// ---- the same passes with one or two heads per offset group (MH kernels): per-output moments, shared layers summed over the outputs
-// d vs [(b, g), J, 2] = the chunk slabs of the group's heads, summed in a fixed order (chunks outer, heads inner)
-__global__ __launch_bounds__(256) void region_dvs_reduce_mh_kernel(const float2* __restrict__ slab, float2* __restrict__ dVS, int B, int H, int G,
-                                                                   int J, int chunks) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)B * G * J) return;
-  const int hpg = H / G;
-  const size_t bg = i / J, j = i - bg * J, b = bg / G, g = bg - b * G, per = (size_t)B * H * J;
-  float2 s = make_float2(0.f, 0.f);
+// ------------------------------------------------------------------------------------------------
+// the dense tail of a region backward, shared by the 2-D region paths and the 1-D piece path (cpb_regions1d.h)
+// ------------------------------------------------------------------------------------------------
+// d vs [(b, g), J] = the chunk slabs [chunk][(b, h)][J] of the group's heads, summed in a fixed order (chunks outer, heads inner).
+// T: a sample position (float2 in 2-D, float in 1-D).  grid (ceil(J / 256), G, B)
+template <typename T>
+__global__ __launch_bounds__(256) void region_dvs_reduce_kernel(const T* __restrict__ slab, T* __restrict__ dVS, int H, int J, int chunks) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= J) return;
+  const int G = gridDim.y, hpg = H / G;
+  const size_t per = (size_t)gridDim.z * H * J, first = ((size_t)blockIdx.z * H + blockIdx.y * hpg) * J + j;
+  T s = slab[first];
   for (int k = 0; k < chunks; ++k)
-    for (int o = 0; o < hpg; ++o) {
-      const float2 t = slab[(size_t)k * per + (b * H + g * hpg + o) * J + j];
-      if (k == 0 && o == 0) s = t;
-      else { s.x += t.x; s.y += t.y; }
-    }
-  dVS[i] = s;
+    for (int o = k ? 0 : 1; o < hpg; ++o) s += slab[(size_t)k * per + first + (size_t)o * J];
+  dVS[((size_t)blockIdx.z * G + blockIdx.y) * J + j] = s;
 }
 
-// The parameter gradients from the moments M_{r,o} of every region r and output o (the formulas of region_final1_kernel with w3 row o):
-// dW2, dW1, db1, db2 are the sums over the outputs (in output order), dW3 [o] and db3 [o] per output.  Slab: dW2 [1024] | dW1 [64] |
-// db1 [32] | db2 [32] | dW3 [hpg * 32] | db3 [hpg]; with one output the layout and every operation are those of region_final1 / 2.
-constexpr int RG_HPG = 2;
-constexpr int RG_GRAD2 = 1152 + RG_HPG * (CH + 1);                  // slab of two outputs (> RG_GRAD)
+// The six parameter gradients from the moments M_{r,o} = sum d bias_o (1, p) of every region (piece) r and output o (o: the head inside
+// its offset group, with row o of w3) - all of them are linear in M:
+//   X1_i = W1[i] . (M1 ..) + b1_i M0,  H1_i = d1_i X1_i;   X2_q = W2[q] . H1 + b2_q M0;   G2_q = d2_q w3[o][q];   C1_i = d1_i sum_q W2[q][i] G2_q
+//   dW3[o][q] += d2_q X2_q;  db3[o] += M0;  db2_q += G2_q M0;  dW2[q][i] += G2_q H1_i;  db1_i += C1_i M0;  dW1[i] += C1_i (M1 ..)
+// dW2, dW1, db1, db2 are the sums over the outputs (each output's sum first, then added in output order).
+// Stage 1: one workgroup per RG_FIN regions -> partial slabs (fp64); stage 2 adds the slabs in order, rescales and scatters.
+// What differs between the paths is a geometry Geo (Region2DGeo below, Region1DGeo in cpb_regions1d.h):
+//   Tables, Pos        the table pointers (with pat and wd) and the type of a sample position
+//   PD                 position components;  W1, B1, W2, B2, w3(o): offsets in the path's fp64 parameter block wd
+//   GROUPS, DIRECT     stage-1 workgroups; whether GRAD holds direct sums (pairs evaluated by the MLP itself: 2-D only)
+//   count(t)           regions in use;  moment(HIST, o, r, m): moment m of (r, o) in the layout the path's moment kernel writes
+//   x1(wd, i, M)       X1_i, in the path's own rounding
+constexpr int RG_FIN = 32, RG_HPG = 2;   // regions per stage-1 workgroup; outputs (heads per offset group) supported: 1 or 2
+// a gradient slab of HPG outputs: dW2 [32][32] | dW1 [32][PD] | db1 | db2 | dW3 [HPG][32] | db3 [HPG]; partial slabs lie STRIDE apart
+template <typename Geo, int HPG>
+struct RegionSlab {
+  static constexpr int W2 = 0, W1 = CH * CH, B1 = W1 + CH * Geo::PD, B2 = B1 + CH, W3 = B2 + CH, B3 = W3 + HPG * CH, N = B3 + HPG;
+  static constexpr int STRIDE = N > RG_GRAD ? N : RG_GRAD;
+};
+struct Region2DGeo {
+  typedef RegionTables Tables;
+  typedef float2 Pos;
+  static constexpr int PD = 2, W1 = WD_W1, B1 = WD_B1, W2 = WD_W2, B2 = WD_B2, GROUPS = RG_RCAP / RG_FIN;
+  static constexpr bool DIRECT = true;
+  __device__ static int w3(int o) { return o ? WD_W3B : WD_W3; }
+  __device__ static int count(const Tables& t) { return (int)t.hdr->n_regions; }
+  __device__ static double moment(const unsigned long long* HIST, int o, int r, int m) {       // [o][RG_RCAP][3]
+    return (double)(long long)HIST[((size_t)o * RG_RCAP + r) * 3 + m];
+  }
+  __device__ static double x1(const double* wd, int i, const double* M) {
+    return wd[W1 + 2 * i] * M[1] + wd[W1 + 2 * i + 1] * M[2] + wd[B1 + i] * M[0];
+  }
+};
+constexpr int RG_GRAD2 = RegionSlab<Region2DGeo, RG_HPG>::STRIDE;  // slab of two outputs (> RG_GRAD)
+static_assert(RegionSlab<Region2DGeo, 1>::N <= RG_GRAD && RG_GRAD2 > RG_GRAD, "gradient slabs");
 __host__ __device__ inline int region_slab_stride(int hpg) { return hpg > 1 ? RG_GRAD2 : RG_GRAD; }
-__global__ __launch_bounds__(256) void region_final1_mh_kernel(RegionTables t, const unsigned long long* __restrict__ HIST, double* __restrict__ part,
-                                                               int hpg) {
-  __shared__ double M[RG_HPG][RG_FIN][3], H1[RG_HPG][RG_FIN][CH], X2[RG_HPG][RG_FIN][CH], C1[RG_HPG][RG_FIN][CH];
+
+template <typename Geo, int HPG>
+__global__ __launch_bounds__(256) void region_final1_kernel(typename Geo::Tables t, const unsigned long long* __restrict__ HIST,
+                                                            double* __restrict__ part) {
+  typedef RegionSlab<Geo, HPG> S;
+  constexpr int NM = Geo::PD + 1;
+  __shared__ double M[HPG][RG_FIN][NM], H1[HPG][RG_FIN][CH], X2[HPG][RG_FIN][CH], C1[HPG][RG_FIN][CH];
   __shared__ unsigned D1[RG_FIN], D2[RG_FIN];
   const int tid = threadIdx.x, r0 = blockIdx.x * RG_FIN;
-  const int nreg = (int)t.hdr->n_regions;
+  const int nreg = Geo::count(t);
   const double* __restrict__ wd = t.wd;
-  for (int x = tid; x < hpg * RG_FIN * 3; x += 256) {
-    const int o = x / (RG_FIN * 3), rr = (x / 3) % RG_FIN, m = x % 3, r = r0 + rr;
-    M[o][rr][m] = r < nreg ? (double)(long long)HIST[((size_t)o * RG_RCAP + r) * 3 + m] : 0.0;
+  for (int x = tid; x < HPG * RG_FIN * NM; x += 256) {
+    const int o = x / (RG_FIN * NM), rr = (x / NM) % RG_FIN, m = x % NM, r = r0 + rr;
+    M[o][rr][m] = r < nreg ? Geo::moment(HIST, o, r, m) : 0.0;
   }
   if (tid < RG_FIN) {
     const int r = r0 + tid;
@@ -1352,50 +1294,46 @@ __global__ __launch_bounds__(256) void region_final1_mh_kernel(RegionTables t, c
     D1[tid] = (unsigned)k; D2[tid] = (unsigned)(k >> 32);
   }
   __syncthreads();
-  for (int x = tid; x < hpg * RG_FIN * CH; x += 256) {
+  for (int x = tid; x < HPG * RG_FIN * CH; x += 256) {
     const int o = x / (RG_FIN * CH), r = (x >> 5) % RG_FIN, i = x & 31;
-    const double x1 = wd[WD_W1 + 2 * i] * M[o][r][1] + wd[WD_W1 + 2 * i + 1] * M[o][r][2] + wd[WD_B1 + i] * M[o][r][0];
-    H1[o][r][i] = ((D1[r] >> i) & 1u) ? x1 : 0.0;
+    H1[o][r][i] = ((D1[r] >> i) & 1u) ? Geo::x1(wd, i, M[o][r]) : 0.0;
   }
   __syncthreads();
-  for (int x = tid; x < hpg * RG_FIN * CH; x += 256) {
+  for (int x = tid; x < HPG * RG_FIN * CH; x += 256) {
     const int o = x / (RG_FIN * CH), r = (x >> 5) % RG_FIN, q = x & 31;
-    const int w3 = o ? WD_W3B : WD_W3;
-    double v = wd[WD_B2 + q] * M[o][r][0];
-    for (int i = 0; i < CH; ++i) v = fma(wd[WD_W2 + q * CH + i], H1[o][r][i], v);
+    double v = wd[Geo::B2 + q] * M[o][r][0];
+    for (int i = 0; i < CH; ++i) v = fma(wd[Geo::W2 + q * CH + i], H1[o][r][i], v);
     X2[o][r][q] = v;
     double cc = 0.0;                                               // C1 of unit i = q
     for (int qq = 0; qq < CH; ++qq)
-      if ((D2[r] >> qq) & 1u) cc = fma(wd[WD_W2 + qq * CH + q], wd[w3 + qq], cc);
+      if ((D2[r] >> qq) & 1u) cc = fma(wd[Geo::W2 + qq * CH + q], wd[Geo::w3(o) + qq], cc);
     C1[o][r][q] = ((D1[r] >> q) & 1u) ? cc : 0.0;
   }
   __syncthreads();
-  const int kw3 = 1152, kb3 = kw3 + hpg * CH, n = kb3 + hpg;
-  double* out = part + (size_t)blockIdx.x * region_slab_stride(hpg);
-  for (int k = tid; k < n; k += 256) {
+  double* out = part + (size_t)blockIdx.x * S::STRIDE;
+  for (int k = tid; k < S::N; k += 256) {
     double v = 0.0;
-    for (int o = 0; o < hpg; ++o) {
-      const int w3 = o ? WD_W3B : WD_W3;
+    for (int o = 0; o < HPG; ++o) {
       double s = 0.0;
-      if (k < 1024) {
+      if (k < S::W1) {
         const int q = k >> 5, i = k & 31;
         for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += H1[o][r][i];
-        s *= wd[w3 + q];
-      } else if (k < 1024 + 64) {
-        const int i = (k - 1024) >> 1, comp = (k - 1024) & 1;
+        s *= wd[Geo::w3(o) + q];
+      } else if (k < S::B1) {
+        const int i = (k - S::W1) / Geo::PD, comp = (k - S::W1) % Geo::PD;
         for (int r = 0; r < RG_FIN; ++r) s = fma(C1[o][r][i], M[o][r][1 + comp], s);
-      } else if (k < 1024 + 96) {
-        const int i = k - 1088;
+      } else if (k < S::B2) {
+        const int i = k - S::B1;
         for (int r = 0; r < RG_FIN; ++r) s = fma(C1[o][r][i], M[o][r][0], s);
-      } else if (k < kw3) {
-        const int q = k - 1120;
+      } else if (k < S::W3) {
+        const int q = k - S::B2;
         for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += M[o][r][0];
-        s *= wd[w3 + q];
-      } else if (k < kb3) {
-        const int oo = (k - kw3) >> 5, q = (k - kw3) & 31;
-        if (oo == o)
+        s *= wd[Geo::w3(o) + q];
+      } else if (k < S::B3) {
+        const int q = (k - S::W3) & 31;
+        if ((k - S::W3) >> 5 == o)
           for (int r = 0; r < RG_FIN; ++r) if ((D2[r] >> q) & 1u) s += X2[o][r][q];
-      } else if (k - kb3 == o) {
+      } else if (k - S::B3 == o) {
         for (int r = 0; r < RG_FIN; ++r) s += M[o][r][0];
       }
       v = o ? v + s : s;
@@ -1403,36 +1341,41 @@ __global__ __launch_bounds__(256) void region_final1_mh_kernel(RegionTables t, c
     out[k] = v;
   }
 }
-// GRAD [outputs][RG_GRAD]: the direct sums of the pairs without a region, per output in the one-output layout.  FLAG != 0 (a non-finite
-// d score): every parameter gradient is NaN.
-__global__ __launch_bounds__(256) void region_final2_mh_kernel(const double* __restrict__ part, int groups, const unsigned long long* __restrict__ GRAD,
-                                                               const unsigned* __restrict__ AMAX, const unsigned* __restrict__ FLAG, int kbits_global,
-                                                               int hpg, float* __restrict__ dW1, float* __restrict__ db1, float* __restrict__ dW2,
-                                                               float* __restrict__ db2, float* __restrict__ dW3, float* __restrict__ db3) {
+// Stage 2.  GRAD [outputs][RG_GRAD] (Geo::DIRECT): the direct sums of the pairs without a region, per output in the one-output slab
+// layout.  AMAX[1] != 0 (a non-finite d score, raised by the moment kernels that look for one): every parameter gradient is NaN.
+template <typename Geo, int HPG>
+__global__ __launch_bounds__(256) void region_final2_kernel(const double* __restrict__ part, const unsigned long long* __restrict__ GRAD,
+                                                            const unsigned* __restrict__ AMAX, int kbits_global, float* __restrict__ dW1,
+                                                            float* __restrict__ db1, float* __restrict__ dW2, float* __restrict__ db2,
+                                                            float* __restrict__ dW3, float* __restrict__ db3) {
+  typedef RegionSlab<Geo, HPG> S;
+  typedef RegionSlab<Geo, 1> S1;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int kw3 = 1152, kb3 = kw3 + hpg * CH, stride = region_slab_stride(hpg);
-  if (k >= kb3 + hpg) return;
-  unsigned long long gi;
-  if (k < kw3) {
-    gi = GRAD[k];
-    for (int o = 1; o < hpg; ++o) gi += GRAD[(size_t)o * RG_GRAD + k];
-  } else if (k < kb3) {
-    gi = GRAD[(size_t)((k - kw3) >> 5) * RG_GRAD + 1152 + ((k - kw3) & 31)];
-  } else {
-    gi = GRAD[(size_t)(k - kb3) * RG_GRAD + 1184];
+  if (k >= S::N) return;
+  double v = 0.0;
+  if constexpr (Geo::DIRECT) {
+    unsigned long long gi;
+    if (k < S::W3) {
+      gi = GRAD[k];
+      for (int o = 1; o < HPG; ++o) gi += GRAD[(size_t)o * RG_GRAD + k];
+    } else if (k < S::B3) {
+      gi = GRAD[(size_t)((k - S::W3) >> 5) * RG_GRAD + S1::W3 + ((k - S::W3) & 31)];
+    } else {
+      gi = GRAD[(size_t)(k - S::B3) * RG_GRAD + S1::B3];
+    }
+    v = (double)(long long)gi;
   }
-  double v = (double)(long long)gi;
-  for (int g = 0; g < groups; ++g) v += part[(size_t)g * stride + k];
+  for (int g = 0; g < Geo::GROUPS; ++g) v += part[(size_t)g * S::STRIDE + k];
   const RegionScale sc = region_scale(*AMAX, kbits_global);
   // the quiet NaN goes out as its bit pattern: this file is built with -fno-honor-nans, under which a NaN constant may be folded away
-  const unsigned r = *FLAG ? 0x7FC00000u : __float_as_uint((float)(v / sc.S));
+  const unsigned r = AMAX[1] ? 0x7FC00000u : __float_as_uint((float)(v / sc.S));
   auto put = [&](float* dst, int i) { reinterpret_cast<unsigned*>(dst)[i] = r; };
-  if (k < 1024) put(dW2, k);
-  else if (k < 1024 + 64) put(dW1, k - 1024);
-  else if (k < 1024 + 96) put(db1, k - 1088);
-  else if (k < kw3) put(db2, k - 1120);
-  else if (k < kb3) put(dW3, k - kw3);
-  else put(db3, k - kb3);
+  if (k < S::W1) put(dW2, k);
+  else if (k < S::B1) put(dW1, k - S::W1);
+  else if (k < S::B2) put(db1, k - S::B1);
+  else if (k < S::W3) put(db2, k - S::B2);
+  else if (k < S::B3) put(dW3, k - S::W3);
+  else put(db3, k - S::B3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1475,16 +1418,15 @@ static RegionBwdPlan region_bwd_plan(int B, int N, int J, int H, int outputs = 1
   return p;
 }
 
-static int check_region(const char* fn, int B, int N, int J, int H) {
-  SMML_REQUIRE(B > 0 && N > 0 && J > 0 && H > 0, "%s: non-positive dimension", fn);
+// dimensions of a region entry point (one head per offset group: G == H).  dims_first: the 1-D entry points name a non-positive dimension
+// before a head count they do not support, the 2-D ones after it.
+static int check_region(const char* fn, int B, int N, int J, int H, int G, bool dims_first = false) {
+  SMML_REQUIRE(G > 0 && !(dims_first && (B <= 0 || N <= 0 || J <= 0 || H <= 0)), "%s: non-positive dimension", fn);
+  SMML_REQUIRE(H > 0 && H % G == 0 && H / G <= RG_HPG, "%s: heads (%d) must be 1 or 2 per offset group (%d groups)", fn, H, G);
+  SMML_REQUIRE(B > 0 && N > 0 && J > 0, "%s: non-positive dimension", fn);
   SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
   SMML_REQUIRE(J <= RG_MAX_KEYS, "%s: the region kernels take at most %d keys (got %d)", fn, RG_MAX_KEYS, J);
   return SMML_OK;
-}
-static int check_region_mh(const char* fn, int B, int N, int J, int H, int G) {
-  SMML_REQUIRE(G > 0, "%s: non-positive dimension", fn);
-  SMML_REQUIRE(H > 0 && H % G == 0 && H / G <= RG_HPG, "%s: heads (%d) must be 1 or 2 per offset group (%d groups)", fn, H, G);
-  return check_region(fn, B, N, J, H);
 }
 static int check_region_workspace(const char* fn, const void* ws, size_t bytes, const RegionBwdPlan& pl, int J) {
   if (int rc = check_workspace(fn, ws, bytes, pl.total, 256)) return rc;
@@ -1497,21 +1439,40 @@ static int region_lcap(const SmmlDeformOpts* opts) {
 }
 
 
+// the dense tail of pass 3, behind the path's moment kernel: d vs from the chunk slabs, then the six parameter gradients from the moments
+template <typename Geo>
+static void region_final_launch(typename Geo::Tables t, char* wsb, const RegionBwdPlan& pl, int B, int J, int H, int G, float* dvs, float* dw1,
+                                float* db1, float* dw2, float* db2, float* dw3, float* db3, hipStream_t st) {
+  typedef typename Geo::Pos Pos;
+  const unsigned* amax = reinterpret_cast<const unsigned*>(wsb + pl.amax);
+  const unsigned long long* hist = reinterpret_cast<const unsigned long long*>(wsb + pl.hist);
+  const unsigned long long* grad = reinterpret_cast<const unsigned long long*>(wsb + pl.grad);
+  double* part = reinterpret_cast<double*>(wsb + pl.part);
+  hipLaunchKernelGGL(region_dvs_reduce_kernel<Pos>, dim3((J + 255) / 256, G, B), dim3(256), 0, st, reinterpret_cast<const Pos*>(wsb + pl.dvs),
+                     reinterpret_cast<Pos*>(dvs), H, J, pl.chunks);
+  auto finals = [&](auto hpg) {
+    constexpr int HPG = decltype(hpg)::value;
+    hipLaunchKernelGGL((region_final1_kernel<Geo, HPG>), dim3(Geo::GROUPS), dim3(256), 0, st, t, hist, part);
+    hipLaunchKernelGGL((region_final2_kernel<Geo, HPG>), dim3((RegionSlab<Geo, HPG>::N + 255) / 256), dim3(256), 0, st, part, grad, amax,
+                       pl.kbits - pl.shift, dw1, db1, dw2, db2, dw3, db3);
+  };
+  if (H / G == 2) finals(std::integral_constant<int, 2>());
+  else finals(std::integral_constant<int, 1>());
+}
+
 // pass 3 of a region backward: d vs per pair, region moments (cpb_region_bwd_kernel<DS>), then the dense pass to the six parameter gradients.
 // wsb: the call's workspace (bytes), pl: its plan; amax | hist | grad were zeroed and amax filled by the dq pass of the caller.
-// MH: the kernels of one or two heads per offset group (G groups; pl planned with H / G outputs); else G == H and one head per group.
+// MH: the moment kernel of one or two heads per offset group (G groups; pl planned with H / G outputs); else G == H and one head per group.
 template <typename DS, bool MH = false>
 static int region_bias_bwd_launch(const char* fn, const DS* dlogits, const unsigned short* region_ids, const float* vs, const float* gq, CpbParams cp,
                                   const void* tables, char* wsb, const RegionBwdPlan& pl, int B, int N, int J, int H, int G, int nst, int lcap,
                                   float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ev_start, void* ev_stop,
                                   hipStream_t st) {
-  const RegionTables rt = region_tables(const_cast<void*>(tables));
   const RegionView rv = region_view(const_cast<void*>(tables));
   unsigned* amax = reinterpret_cast<unsigned*>(wsb + pl.amax);
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(wsb + pl.hist);
   unsigned long long* grad = reinterpret_cast<unsigned long long*>(wsb + pl.grad);
   float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
-  double* part = reinterpret_cast<double*>(wsb + pl.part);
   {   // 89 KB of dynamic LDS: above the 64 KB a kernel gets without asking (a host-side attribute of the function: cheap, idempotent)
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cpb_region_bwd_kernel<DS, MH>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RegionBwdLds));
@@ -1523,23 +1484,7 @@ static int region_bias_bwd_launch(const char* fn, const DS* dlogits, const unsig
                      pl.kbits, pl.shift, lcap, G);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
   SMML_LAUNCH_CHECK(fn);
-  const int groups = RG_RCAP / RG_FIN;
-  if (MH) {
-    const int hpg = H / G;
-    const size_t n = (size_t)B * G * J;
-    hipLaunchKernelGGL(region_dvs_reduce_mh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(dvs_slab),
-                       reinterpret_cast<float2*>(dvs), B, H, G, J, pl.chunks);
-    hipLaunchKernelGGL(region_final1_mh_kernel, dim3(groups), dim3(256), 0, st, rt, hist, part, hpg);
-    hipLaunchKernelGGL(region_final2_mh_kernel, dim3((RG_GRAD2 + 255) / 256), dim3(256), 0, st, part, groups, grad, amax, amax + 1,
-                       pl.kbits - pl.shift, hpg, dw1, db1, dw2, db2, dw3, db3);
-  } else {
-    const size_t n = (size_t)B * H * J;
-    hipLaunchKernelGGL(region_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float2*>(dvs_slab),
-                       reinterpret_cast<float2*>(dvs), n, pl.chunks);
-    hipLaunchKernelGGL(region_final1_kernel, dim3(groups), dim3(256), 0, st, rt, hist, part);
-    hipLaunchKernelGGL(region_final2_kernel, dim3((RG_GRAD + 255) / 256), dim3(256), 0, st, part, groups, grad, amax, pl.kbits - pl.shift, dw1, db1,
-                       dw2, db2, dw3, db3);
-  }
+  region_final_launch<Region2DGeo>(region_tables(const_cast<void*>(tables)), wsb, pl, B, J, H, G, dvs, dw1, db1, dw2, db2, dw3, db3, st);
   SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }

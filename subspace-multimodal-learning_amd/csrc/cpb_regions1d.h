@@ -555,119 +555,21 @@ __global__ __launch_bounds__(768) void cpb_region1d_bwd_kernel(
   }
 }
 
-// d vs [(b, g), J] = the chunk slabs of the group's heads, summed in a fixed order (chunks outer, heads inner)
-__global__ __launch_bounds__(256) void region1d_dvs_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dVS, int B, int H, int G,
-                                                                  int J, int chunks) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t n = (size_t)B * G * J;
-  if (i >= n) return;
-  const int hpg = H / G;
-  const size_t bg = i / J, j = i - bg * J;
-  const size_t b = bg / G, g = bg - b * G;
-  const size_t per = (size_t)B * H * J;
-  float s = 0.f;
-  for (int k = 0; k < chunks; ++k)
-    for (int o = 0; o < hpg; ++o) s += slab[(size_t)k * per + ((b * H + g * hpg + o) * J) + j];
-  dVS[i] = s;
-}
-
-// The six parameter gradients from the piece moments M_{r,o} = sum d bias_o (1, p), all linear in M:
-//   H1_i = d1_i (w1_i M1 + b1_i M0);  X2_q = W2[q] . H1 + b2_q M0;  G2_q = d2_q w3[o][q];  C1_i = d1_i sum_q W2[q][i] G2_q
-//   dW2[q][i] += G2_q H1_i;  dw1_i += C1_i M1;  db1_i += C1_i M0;  db2_q += G2_q M0;  dW3[o][q] += d2_q X2_q;  db3[o] += M0
-// Slab: dW2 [1024] | dw1 [32] | db1 [32] | db2 [32] | dW3 [hpg * 32] | db3 [hpg] (<= RG_GRAD).  Stage 1: 32 pieces per workgroup ->
-// fp64 partial slabs; stage 2 adds them in order.
-constexpr int R1_FIN = 32, R1_GROUPS = (R1_MAXP + R1_FIN - 1) / R1_FIN;
-constexpr int R1G_W2 = 0, R1G_W1 = 1024, R1G_B1 = 1056, R1G_B2 = 1088, R1G_W3 = 1120, R1G_B3 = 1184, R1G_N = 1186;
-static_assert(R1G_N <= RG_GRAD, "1-D gradient slab");
-__global__ __launch_bounds__(256) void region1d_final1_kernel(Region1DTables t, const unsigned long long* __restrict__ HIST, double* __restrict__ part) {
-  __shared__ double M[R1_FIN][R1_HPG][2], H1[R1_FIN][R1_HPG][CH], X2[R1_FIN][R1_HPG][CH], C1[R1_FIN][R1_HPG][CH];
-  __shared__ unsigned D1[R1_FIN], D2[R1_FIN];
-  const int tid = threadIdx.x, r0 = blockIdx.x * R1_FIN;
-  const int npc = min((int)t.hdr->n_bp, R1_MAXBP) + 1, hpg = min((int)t.hdr->hpg, R1_HPG);
-  const double* __restrict__ wd = t.wd;
-  if (tid < R1_FIN * R1_HPG * 2) {
-    const int r = tid / (R1_HPG * 2), k = tid - r * (R1_HPG * 2);
-    M[r][k >> 1][k & 1] = (r0 + r < npc) ? (double)(long long)HIST[(size_t)(r0 + r) * R1_HPG * 2 + k] : 0.0;
+// the 1-D geometry of the dense tail (region_final_launch, cpb_regions.h): two moments (1, p) per piece and output
+struct Region1DGeo {
+  typedef Region1DTables Tables;
+  typedef float Pos;
+  static constexpr int PD = 1, W1 = W1D_W1, B1 = W1D_B1, W2 = W1D_W2, B2 = W1D_B2, GROUPS = (R1_MAXP + RG_FIN - 1) / RG_FIN;
+  static constexpr bool DIRECT = false;
+  __device__ static int w3(int o) { return W1D_W3 + o * CH; }
+  __device__ static int count(const Tables& t) { return min((int)t.hdr->n_bp, R1_MAXBP) + 1; }
+  __device__ static double moment(const unsigned long long* HIST, int o, int r, int m) {       // [piece][R1_HPG][2]
+    return (double)(long long)HIST[((size_t)r * R1_HPG + o) * 2 + m];
   }
-  if (tid < R1_FIN) {
-    const unsigned long long k = (r0 + tid < npc) ? t.pat[r0 + tid] : 0ull;
-    D1[tid] = (unsigned)k; D2[tid] = (unsigned)(k >> 32);
-  }
-  __syncthreads();
-  for (int x = tid; x < R1_FIN * R1_HPG * CH; x += 256) {
-    const int r = x / (R1_HPG * CH), o = (x / CH) % R1_HPG, i = x % CH;
-    H1[r][o][i] = ((D1[r] >> i) & 1u) ? fma(wd[W1D_W1 + i], M[r][o][1], wd[W1D_B1 + i] * M[r][o][0]) : 0.0;
-  }
-  __syncthreads();
-  for (int x = tid; x < R1_FIN * R1_HPG * CH; x += 256) {
-    const int r = x / (R1_HPG * CH), o = (x / CH) % R1_HPG, q = x % CH;
-    double v = wd[W1D_B2 + q] * M[r][o][0];
-    for (int i = 0; i < CH; ++i) v = fma(wd[W1D_W2 + q * CH + i], H1[r][o][i], v);
-    X2[r][o][q] = v;
-    double cc = 0.0;                                               // C1 of unit i = q
-    if (o < hpg)
-      for (int qq = 0; qq < CH; ++qq)
-        if ((D2[r] >> qq) & 1u) cc = fma(wd[W1D_W2 + qq * CH + q], wd[W1D_W3 + o * CH + qq], cc);
-    C1[r][o][q] = ((D1[r] >> q) & 1u) ? cc : 0.0;
-  }
-  __syncthreads();
-  double* out = part + (size_t)blockIdx.x * RG_GRAD;
-  for (int k = tid; k < RG_GRAD; k += 256) {
-    double v = 0.0;
-    for (int o = 0; o < hpg; ++o) {
-      if (k < R1G_W1) {
-        const int q = k >> 5, i = k & 31;
-        double s = 0.0;
-        for (int r = 0; r < R1_FIN; ++r) if ((D2[r] >> q) & 1u) s += H1[r][o][i];
-        v = fma(s, wd[W1D_W3 + o * CH + q], v);
-      } else if (k < R1G_B1) {
-        for (int r = 0; r < R1_FIN; ++r) v = fma(C1[r][o][k - R1G_W1], M[r][o][1], v);
-      } else if (k < R1G_B2) {
-        for (int r = 0; r < R1_FIN; ++r) v = fma(C1[r][o][k - R1G_B1], M[r][o][0], v);
-      } else if (k < R1G_W3) {
-        const int q = k - R1G_B2;
-        double s = 0.0;
-        for (int r = 0; r < R1_FIN; ++r) if ((D2[r] >> q) & 1u) s += M[r][o][0];
-        v = fma(s, wd[W1D_W3 + o * CH + q], v);
-      } else if (k < R1G_B3) {
-        const int oo = (k - R1G_W3) >> 5, q = (k - R1G_W3) & 31;
-        if (oo == o)
-          for (int r = 0; r < R1_FIN; ++r) if ((D2[r] >> q) & 1u) v += X2[r][o][q];
-      } else if (k < R1G_N) {
-        if (k - R1G_B3 == o)
-          for (int r = 0; r < R1_FIN; ++r) v += M[r][o][0];
-      }
-    }
-    out[k] = v;
-  }
-}
-__global__ __launch_bounds__(256) void region1d_final2_kernel(const double* __restrict__ part, const unsigned* __restrict__ AMAX,
-                                                              const unsigned* __restrict__ FLAG, int kbits_global, int hpg, float* __restrict__ dW1,
-                                                              float* __restrict__ db1, float* __restrict__ dW2, float* __restrict__ db2,
-                                                              float* __restrict__ dW3, float* __restrict__ db3) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= R1G_N) return;
-  double v = 0.0;
-  for (int gi = 0; gi < R1_GROUPS; ++gi) v += part[(size_t)gi * RG_GRAD + k];
-  const RegionScale sc = region_scale(*AMAX, kbits_global);
-  // the quiet NaN goes out as its bit pattern: this file is built with -fno-honor-nans, under which a NaN constant may be folded away
-  const unsigned r = *FLAG ? 0x7FC00000u : __float_as_uint((float)(v / sc.S));
-  auto put = [&](float* dst, int i) { reinterpret_cast<unsigned*>(dst)[i] = r; };
-  if (k < R1G_W1) put(dW2, k);
-  else if (k < R1G_B1) put(dW1, k - R1G_W1);
-  else if (k < R1G_B2) put(db1, k - R1G_B1);
-  else if (k < R1G_W3) put(db2, k - R1G_B2);
-  else if (k < R1G_B3) { if (k - R1G_W3 < hpg * CH) put(dW3, k - R1G_W3); }
-  else if (k - R1G_B3 < hpg) put(db3, k - R1G_B3);
-}
-
-static int check_region1d(const char* fn, int B, int N, int J, int H, int G) {
-  SMML_REQUIRE(B > 0 && N > 0 && J > 0 && H > 0 && G > 0, "%s: non-positive dimension", fn);
-  SMML_REQUIRE(H % G == 0 && H / G <= R1_HPG, "%s: heads (%d) must be 1 or 2 per offset group (%d groups)", fn, H, G);
-  SMML_REQUIRE(deform_dims_ok(B, N, J, H), "%s: B, H <= 65535, N <= 2^26, J <= 2^22 (got B %d N %d J %d H %d)", fn, B, N, J, H);
-  SMML_REQUIRE(J <= RG_MAX_KEYS, "%s: the region kernels take at most %d keys (got %d)", fn, RG_MAX_KEYS, J);
-  return SMML_OK;
-}
+  __device__ static double x1(const double* wd, int i, const double* M) { return fma(wd[W1 + i], M[1], wd[B1 + i] * M[0]); }
+};
+static_assert(R1_HPG == RG_HPG && RegionSlab<Region1DGeo, R1_HPG>::STRIDE == RG_GRAD && Region1DGeo::GROUPS <= Region2DGeo::GROUPS,
+              "the 1-D backward runs in the workspace of region_bwd_plan");
 
 // pass 3 of a piece backward: d vs per pair and piece moments (cpb_region1d_bwd_kernel), then the dense pass to the six parameter gradients.
 // wsb: the call's workspace (bytes), pl: its plan (region_bwd_plan); amax | flag | hist | grad were zeroed and amax filled by the dq pass.
@@ -679,18 +581,13 @@ static int region1d_bias_bwd_launch(const char* fn, const float* dlogits, const 
   unsigned* flag = amax + 1;                                 // non-finite d score seen (same zeroed 256-byte block)
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(wsb + pl.hist);
   float* dvs_slab = reinterpret_cast<float*>(wsb + pl.dvs);
-  double* part = reinterpret_cast<double*>(wsb + pl.part);
   const Region1DView rv = region1d_view(tables);
   if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
   hipLaunchKernelGGL(cpb_region1d_bwd_kernel, dim3(pl.chunks * pl.ngrp, H, B), dim3(64 * pl.nkbg * pl.wpk), 0, st, dlogits, region_ids, vs, gq, rv,
                      amax, flag, hist, dvs_slab, N, J, H, G, nst, pl.nkb, pl.nkbg, pl.chunks, pl.wpk, pl.tiles_per_chunk, pl.kbits, pl.shift);
   if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
   if (int rc = launch_check(fn, "cpb")) return rc;
-  const size_t n = (size_t)B * G * J;
-  hipLaunchKernelGGL(region1d_dvs_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dvs_slab, dvs, B, H, G, J, pl.chunks);
-  hipLaunchKernelGGL(region1d_final1_kernel, dim3(R1_GROUPS), dim3(256), 0, st, region1d_tables(const_cast<void*>(tables)), hist, part);
-  hipLaunchKernelGGL(region1d_final2_kernel, dim3((R1G_N + 255) / 256), dim3(256), 0, st, part, amax, flag, pl.kbits - pl.shift, H / G, dw1, db1, dw2,
-                     db2, dw3, db3);
+  region_final_launch<Region1DGeo>(region1d_tables(const_cast<void*>(tables)), wsb, pl, B, J, H, G, dvs, dw1, db1, dw2, db2, dw3, db3, st);
   return launch_check(fn, "reduce");
 }
 

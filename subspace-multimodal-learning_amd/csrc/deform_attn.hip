@@ -1279,21 +1279,25 @@ int smml_deform_attn_bwd_f32(const float* q, const float* k, const float* v, con
 // ------------------------------------------------------------------------------------------------
 // position bias per linear region (cpb_regions.h): exact, 2-D signed-log offsets, one head per offset group
 // ------------------------------------------------------------------------------------------------
-size_t smml_cpb_regions_bytes(void) { return region_layout().total; }
+}  // extern "C"
 
-int smml_cpb_regions_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
-                           float pmax, void* tables, size_t tables_bytes, void* stream) {
-  SMML_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && tables, "smml_cpb_regions_build: null pointer");
-  SMML_REQUIRE(pmax > 0.f && pmax < 16.f, "smml_cpb_regions_build: pmax must be in (0, 16) (got %g)", (double)pmax);
-  SMML_REQUIRE(tables_bytes >= region_layout().total, "smml_cpb_regions_build: table buffer too small (%zu < %zu)", tables_bytes,
-               region_layout().total);
-  SMML_REQUIRE((reinterpret_cast<size_t>(tables) & 255) == 0, "smml_cpb_regions_build: table buffer must be 256-byte aligned");
-  region_build_launch(CpbParams{w1, b1, w2, b2, w3, b3}, pmax, tables, (hipStream_t)stream);
-  SMML_LAUNCH_CHECK("smml_cpb_regions_build");
+// the table build of the 2-D region entry points (outputs: heads per offset group)
+static int regions_build(const char* fn, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                         int outputs, float pmax, void* tables, size_t tables_bytes, void* stream) {
+  SMML_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && tables, "%s: null pointer", fn);
+  SMML_REQUIRE(outputs == 1 || outputs == 2, "%s: outputs (heads per offset group) must be 1 or 2 (got %d)", fn, outputs);
+  SMML_REQUIRE(pmax > 0.f && pmax < 16.f, "%s: pmax must be in (0, 16) (got %g)", fn, (double)pmax);
+  SMML_REQUIRE(tables_bytes >= region_layout().total, "%s: table buffer too small (%zu < %zu)", fn, tables_bytes, region_layout().total);
+  SMML_REQUIRE((reinterpret_cast<size_t>(tables) & 255) == 0, "%s: table buffer must be 256-byte aligned", fn);
+  region_build_launch(CpbParams{w1, b1, w2, b2, w3, b3}, pmax, tables, (hipStream_t)stream, outputs);
+  SMML_LAUNCH_CHECK(fn);
   return SMML_OK;
 }
-
-}  // extern "C"
+// workspace of a region backward with H / G outputs (0: sizes no region entry point takes)
+static size_t region_bwd_bytes(int B, int N, int J, int H, int G) {
+  if (!deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS || G <= 0 || H % G || H / G > RG_HPG) return 0;
+  return region_bwd_plan(B, N, J, H, H / G).total;
+}
 
 // the region forward of one head per offset group (G == H) or, MH, of one or two heads per group
 template <bool MH>
@@ -1301,7 +1305,7 @@ static int region_fwd_f32(const char* fn, const float* q, const float* k, const 
                           const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const void* tables, float* out,
                           float* lse, float* logits_t, unsigned short* region_ids, int B, int N, int J, int H, int G, float scale, float dropout_p,
                           unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  int rc = check_region(fn, B, N, J, H, G);
   if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && lse, "%s: null pointer", fn);
@@ -1326,13 +1330,13 @@ static int region_bwd_f32(const char* fn, const float* q, const float* k, const 
                           float* dk, float* dv, float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
                           size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p, unsigned long long dropout_seed,
                           void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
-  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  int rc = check_region(fn, B, N, J, H, G);
   if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits_t && region_ids &&
                    dlogits_t && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
                "%s: null pointer", fn);
-  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, MH ? H / G : 1);
+  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, H / G);
   if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   hipStream_t st = (hipStream_t)stream;
@@ -1348,6 +1352,13 @@ static int region_bwd_f32(const char* fn, const float* q, const float* k, const 
 
 extern "C" {
 
+size_t smml_cpb_regions_bytes(void) { return region_layout().total; }
+
+int smml_cpb_regions_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                           float pmax, void* tables, size_t tables_bytes, void* stream) {
+  return regions_build("smml_cpb_regions_build", w1, b1, w2, b2, w3, b3, 1, pmax, tables, tables_bytes, stream);
+}
+
 int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                     const float* b3, const void* tables, float* out, float* lse, float* logits_t,
@@ -1358,8 +1369,7 @@ int smml_deform_attn_region_fwd_f32(const float* q, const float* k, const float*
 }
 
 size_t smml_deform_attn_region_bwd_workspace_bytes(int B, int N, int J, int H) {
-  if (!deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS) return 0;
-  return region_bwd_plan(B, N, J, H).total;
+  return region_bwd_bytes(B, N, J, H, H);
 }
 
 int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq,
@@ -1378,15 +1388,7 @@ int smml_deform_attn_region_bwd_f32(const float* q, const float* k, const float*
 // h % (H / G) and the sample positions of group h / (H / G)
 int smml_cpb_regions_mh_build(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int outputs,
                               float pmax, void* tables, size_t tables_bytes, void* stream) {
-  static const char* fn = "smml_cpb_regions_mh_build";
-  SMML_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && tables, "%s: null pointer", fn);
-  SMML_REQUIRE(outputs == 1 || outputs == 2, "%s: outputs (heads per offset group) must be 1 or 2 (got %d)", fn, outputs);
-  SMML_REQUIRE(pmax > 0.f && pmax < 16.f, "%s: pmax must be in (0, 16) (got %g)", fn, (double)pmax);
-  SMML_REQUIRE(tables_bytes >= region_layout().total, "%s: table buffer too small (%zu < %zu)", fn, tables_bytes, region_layout().total);
-  SMML_REQUIRE((reinterpret_cast<size_t>(tables) & 255) == 0, "%s: table buffer must be 256-byte aligned", fn);
-  region_build_launch(CpbParams{w1, b1, w2, b2, w3, b3}, pmax, tables, (hipStream_t)stream, outputs);
-  SMML_LAUNCH_CHECK(fn);
-  return SMML_OK;
+  return regions_build("smml_cpb_regions_mh_build", w1, b1, w2, b2, w3, b3, outputs, pmax, tables, tables_bytes, stream);
 }
 
 int smml_deform_attn_region_mh_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
@@ -1399,8 +1401,7 @@ int smml_deform_attn_region_mh_fwd_f32(const float* q, const float* k, const flo
 }
 
 size_t smml_deform_attn_region_mh_bwd_workspace_bytes(int B, int N, int J, int H, int G) {
-  if (B <= 0 || N <= 0 || J <= 0 || H <= 0 || G <= 0 || H % G || H / G > RG_HPG || !deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS) return 0;
-  return region_bwd_plan(B, N, J, H, H / G).total;
+  return region_bwd_bytes(B, N, J, H, G);
 }
 
 int smml_deform_attn_region_mh_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
@@ -1438,7 +1439,7 @@ int smml_deform_attn_region1d_fwd_f32(const float* q, const float* k, const floa
                                       float scale, float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop,
                                       void* stream, const SmmlDeformOpts* opts) {
   static const char* fn = "smml_deform_attn_region1d_fwd_f32";
-  int rc = check_region1d(fn, B, N, J, H, G);
+  int rc = check_region(fn, B, N, J, H, G, true);
   if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && tables && out && lse, "%s: null pointer", fn);
@@ -1457,8 +1458,7 @@ int smml_deform_attn_region1d_fwd_f32(const float* q, const float* k, const floa
 }
 
 size_t smml_deform_attn_region1d_bwd_workspace_bytes(int B, int N, int J, int H) {
-  if (B <= 0 || N <= 0 || J <= 0 || H <= 0 || !deform_dims_ok(B, N, J, H) || J > RG_MAX_KEYS) return 0;
-  return region_bwd_plan(B, N, J, H).total;
+  return region_bwd_bytes(B, N, J, H, H);          // (the piece moments of both outputs fit the one-output plan)
 }
 
 int smml_deform_attn_region1d_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const void* tables,
@@ -1468,7 +1468,7 @@ int smml_deform_attn_region1d_bwd_f32(const float* q, const float* k, const floa
                                       size_t workspace_bytes, int B, int N, int J, int H, int G, float scale, float dropout_p,
                                       unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts) {
   static const char* fn = "smml_deform_attn_region1d_bwd_f32";
-  int rc = check_region1d(fn, B, N, J, H, G);
+  int rc = check_region(fn, B, N, J, H, G, true);
   if (!rc) rc = check_dropout(fn, dropout_p);
   if (rc) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && tables && out && dout && lse && logits_t && region_ids && dlogits_t && dq && dk && dv && dvs &&

@@ -1510,7 +1510,7 @@ static int region16_fwd(const char* fn, const float* q, const float* k, const fl
                         float* lse, unsigned short* logits16, unsigned short* region_ids, int B, int N, int J, int H, int G, float scale,
                         float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
                         const SmmlDeformOpts* opts) {
-  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  int rc = check_region(fn, B, N, J, H, G);
   if (rc) return rc;
   SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
   if ((rc = check_dropout(fn, dropout_p))) return rc;
@@ -1538,14 +1538,14 @@ static int region16_bwd(const char* fn, const float* q, const float* k, const fl
                         float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B, int N, int J, int H, int G, float scale,
                         float dropout_p, unsigned long long dropout_seed, int dtype, void* ev_start, void* ev_stop, void* stream,
                         const SmmlDeformOpts* opts) {
-  int rc = MH ? check_region_mh(fn, B, N, J, H, G) : check_region(fn, B, N, J, H);
+  int rc = check_region(fn, B, N, J, H, G);
   if (rc) return rc;
   SMML_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype must be 0 (bf16) or 1 (fp16), got %d", fn, dtype);
   if ((rc = check_dropout(fn, dropout_p))) return rc;
   SMML_REQUIRE(q && k && v && vs && gq && w1 && b1 && w2 && b2 && w3 && b3 && tables && out && dout && lse && logits16 && region_ids &&
                    dlogits16 && dq && dk && dv && dvs && dw1 && db1 && dw2 && db2 && dw3 && db3 && workspace,
                "%s: null pointer", fn);
-  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, MH ? H / G : 1);
+  const RegionBwdPlan pl = region_bwd_plan(B, N, J, H, H / G);
   if ((rc = check_region_workspace(fn, workspace, workspace_bytes, pl, J))) return rc;
   const DropCfg dc = make_drop(dropout_p, dropout_seed, opts);
   hipStream_t st = (hipStream_t)stream;

@@ -971,46 +971,35 @@ def cpb_regions1d_build(w1, b1, w2, b2, w3, b3, pmax: float = 0.0, tables: Optio
     return tables
 
 
-def _region1d_why(posdim: int, keys: int, w2_shape, w3_shape, heads: int, groups: int, compute_dtype, cpb_table, log_distance: bool):
-    if posdim != 1:
-        return "the piece path is the 1-D position bias (posdim 1)"
+def _region_why(posdim: int, keys: int, w2_shape, w3_shape, heads: int, groups: int, compute_dtype, cpb_table, cpb_regions, log_distance: bool,
+                region_pmax_given: bool, capturing: bool):
+    """Why the exact position-bias path asked for (posdim 1: per linear piece; posdim 2: per linear region, one or two heads per offset
+    group) cannot take a call; None: it can.  The rules of both, in the order each reports them."""
+    hpg = heads // groups if groups > 0 and heads % groups == 0 else 0
     if not log_distance:
         return "raw distances (cpb_log_distance=False)"
-    if compute_dtype is not None:
+    if posdim == 1 and compute_dtype is not None:
         return "the 16-bit compute modes"
     if cpb_table:
         return "the table modes"
-    if heads % groups or heads // groups not in (1, 2):
-        return f"heads // groups = {heads // groups if groups else 0} (supported: 1, 2)"
+    if cpb_regions is not None and not bool(cpb_regions):
+        return "cpb_regions=False (the per-pair kernels)"
+    if hpg not in (1, 2):
+        return f"heads // groups = {heads // groups if groups > 0 else 0} (supported: 1, 2)"
     if keys > REGION_MAX_KEYS:
         return f"{keys} keys (at most {REGION_MAX_KEYS})"
-    if tuple(w2_shape) != (32, 32) or tuple(w3_shape) != (heads // groups, 32):
-        return "a bias MLP other than 1 -> 32 -> 32 -> heads // groups"
+    if tuple(w2_shape) != (32, 32) or tuple(w3_shape) != (hpg, 32):
+        return f"a bias MLP other than {posdim} -> 32 -> 32 -> heads // groups"
+    if posdim == 2 and capturing and not region_pmax_given:
+        return "a hipGraph capture without cpb_region_pmax (its pmax would come from the data: a host sync)"
     return None
 
 
 def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtype=None, cpb_table=False, log_distance: bool = True):
     """Why the 1-D piece path cannot take this call (None: it can)."""
-    return _region1d_why(vs.shape[-1], k.shape[1], w2.shape, w3.shape, heads, groups, compute_dtype, cpb_table, log_distance)
-
-
-def _region_mh_why(keys: int, w2_shape, w3_shape, heads: int, groups: int, cpb_table, cpb_regions, log_distance: bool, region_pmax_given: bool,
-                   capturing: bool):
-    if not log_distance:
-        return "raw distances (cpb_log_distance=False)"
-    if cpb_table:
-        return "the table modes"
-    if cpb_regions is not None and not bool(cpb_regions):
-        return "cpb_regions=False (the per-pair kernels)"
-    if groups <= 0 or heads % groups or heads // groups not in (1, 2):
-        return f"heads // groups = {heads // groups if groups > 0 else 0} (supported: 1, 2)"
-    if keys > REGION_MAX_KEYS:
-        return f"{keys} keys (at most {REGION_MAX_KEYS})"
-    if tuple(w2_shape) != (32, 32) or tuple(w3_shape) != (heads // groups, 32):
-        return "a bias MLP other than 2 -> 32 -> 32 -> heads // groups"
-    if capturing and not region_pmax_given:
-        return "a hipGraph capture without cpb_region_pmax (its pmax would come from the data: a host sync)"
-    return None
+    if vs.shape[-1] != 1:
+        return "the piece path is the 1-D position bias (posdim 1)"
+    return _region_why(1, k.shape[1], w2.shape, w3.shape, heads, groups, compute_dtype, cpb_table, True, log_distance, True, False)
 
 
 def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32, 32), w3_shape=(1, 32), log_distance: bool = True,
@@ -1026,13 +1015,14 @@ def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32
         raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
     if cpb_regions is not None and bool(cpb_regions) and posdim == 1:
         # 1-D positions: the piece path only on request (cpb_regions=True), and never a silent fall-back from it
-        why = _region1d_why(posdim, keys, w2_shape, w3_shape, heads, groups, compute_dtype, cpb_table, log_distance)
+        why = _region_why(1, keys, w2_shape, w3_shape, heads, groups, compute_dtype, cpb_table, True, log_distance, True, False)
         if why is not None:
             raise ValueError(f"cpb_regions=True with 1-D positions: the piece path does not support {why}")
         return "region1d"
     if regions_multi_head and posdim == 2:
         _dtype16(compute_dtype)
-        why = _region_mh_why(keys, w2_shape, w3_shape, heads, groups, cpb_table, cpb_regions, log_distance, region_pmax_given, capturing)
+        why = _region_why(2, keys, w2_shape, w3_shape, heads, groups, compute_dtype, cpb_table, cpb_regions, log_distance, region_pmax_given,
+                          capturing)
         if why is not None:
             raise ValueError(f"cpb_regions_multi_head=True: the 2-D region path does not support {why}")
         return "region"
@@ -1090,6 +1080,31 @@ def _grads(ctx, *grads):
     return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
+# (1-D, multi-head, 16-bit) -> the region entry points' stem in include/smml.h ("smml_" + stem + "_fwd" / "_bwd", "_f32" behind the fp32-grade
+# ones), their workspace-size function, the TIMER events of the forward and of the bias backward, the stem of the capi.check names
+_REGION_ENTRY = {
+    (True, False, False): ("deform_attn_region1d", "smml_deform_attn_region1d_bwd_workspace_bytes", "deform_region1d_fwd", "cpb_region1d_bwd"),
+    (False, False, False): ("deform_attn_region", "smml_deform_attn_region_bwd_workspace_bytes", "deform_region_fwd", "cpb_region_bwd"),
+    (False, False, True): ("deform_attn16_region", "smml_deform_attn_region_bwd_workspace_bytes", "deform16_region_fwd", "cpb16_region_bwd"),
+    (False, True, False): ("deform_attn_region_mh", "smml_deform_attn_region_mh_bwd_workspace_bytes", "deform_region_mh_fwd", "cpb_region_mh_bwd"),
+    (False, True, True): ("deform_attn16_region_mh", "smml_deform_attn_region_mh_bwd_workspace_bytes", "deform16_region_mh_fwd",
+                          "cpb16_region_mh_bwd"),
+}
+
+
+def _region_entry(ctx, vs, direction: str):
+    """Of this call's region launch in `direction` ('fwd' / 'bwd'): the C entry point, its heads / groups and dtype arguments, the
+    workspace-size function and its arguments, the TIMER event and the capi.check name."""
+    heads, groups, m16 = ctx.cfg[0], ctx.cfg[1], ctx.cfg[5]
+    one_d = vs.shape[-1] == 1
+    stem, ws, ev_fwd, ev_bwd = _REGION_ENTRY[(one_d, ctx.multi_head, m16 is not None)]
+    L = capi.lib()
+    fn = getattr(L, f"smml_{stem}_{direction}" + ("" if m16 is not None else "_f32"))
+    hg = (heads, groups) if one_d or ctx.multi_head else (heads,)
+    return (fn, hg, () if m16 is None else (m16[0],), getattr(L, ws), (heads, groups) if ctx.multi_head else (heads,),
+            ev_fwd if direction == "fwd" else ev_bwd, f"{stem}_{direction}")
+
+
 class _DeformAttnRegion(torch.autograd.Function):
     """The fused core with the position bias per linear region of its MLP (include/smml.h): 2-D (csrc/cpb_regions.h; fp32-grade or, with
     compute_dtype, the 16-bit core) or 1-D per linear piece (csrc/cpb_regions1d.h; fp32-grade core).  pmax: half-width of the tables'
@@ -1106,7 +1121,6 @@ class _DeformAttnRegion(torch.autograd.Function):
         J = k.shape[1]
         one_d = vs.shape[-1] == 1
         _check_core(q, heads, w2)
-        L = capi.lib()
         m16 = _dtype16(compute_dtype)
         if one_d:
             tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
@@ -1119,27 +1133,12 @@ class _DeformAttnRegion(torch.autograd.Function):
         if any(ctx.needs_input_grad):
             logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)
             rid = _score_tiles(q, heads, J, torch.int16)          # the linear piece of every pair, per head
-        pairs = B * heads * N * J
-        qkv = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
-        if one_d:
-            capi.check(L.smml_deform_attn_region1d_fwd_f32(*qkv, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid),
-                                                           B, N, J, heads, groups, float(scale), float(dropout_p), int(dropout_seed),
-                                                           *TIMER.events("deform_region1d_fwd", pairs), capi.stream(), capi.deform_opts(seed_offset)),
-                       "deform_attn_region1d_fwd")
-        else:
-            ropts = capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)
-            w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
-            if ctx.multi_head:
-                fn, ev, name, dt = ((L.smml_deform_attn_region_mh_fwd_f32, "deform_region_mh_fwd", "deform_attn_region_mh_fwd", ()) if m16 is None
-                                    else (L.smml_deform_attn16_region_mh_fwd, "deform16_region_mh_fwd", "deform_attn16_region_mh_fwd", (m16[0],)))
-                hg = (heads, groups)
-            else:
-                fn, ev, name, dt = ((L.smml_deform_attn_region_fwd_f32, "deform_region_fwd", "deform_attn_region_fwd", ()) if m16 is None else
-                                    (L.smml_deform_attn16_region_fwd, "deform16_region_fwd", "deform_attn16_region_fwd", (m16[0],)))
-                hg = (heads,)
-            capi.check(fn(*qkv, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), B, N, J, *hg, float(scale),
-                          float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), ropts), name)
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
+        fn, hg, dt, _, _, ev, name = _region_entry(ctx, vs, "fwd")
+        w = () if one_d else tuple(capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3))        # (the 1-D tables carry the parameters)
+        capi.check(fn(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse),
+                      capi.ptr(logits), capi.ptr(rid), B, N, J, *hg, float(scale), float(dropout_p), int(dropout_seed), *dt,
+                      *TIMER.events(ev, B * heads * N * J), capi.stream(), capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
         # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
         if DECISION_TAP is not None:
@@ -1152,39 +1151,21 @@ class _DeformAttnRegion(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
+        heads, _, scale, dropout_p, dropout_seed, m16 = ctx.cfg
         B, N, _ = q.shape
         J = k.shape[1]
-        L = capi.lib()
         dout = _c(dout)
         dlogits = _dscores(logits, m16)
         dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
-        pairs = B * heads * N * J
-        fwd = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
         grads = (capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs), capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2),
                  capi.fptr(dw3), capi.fptr(db3))
-        if vs.shape[-1] == 1:
-            wsb = L.smml_deform_attn_region1d_bwd_workspace_bytes(B, N, J, heads)
-            ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
-            capi.check(L.smml_deform_attn_region1d_bwd_f32(
-                *fwd, capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse), capi.fptr(logits), capi.ptr(rid), capi.fptr(dlogits),
-                *grads, capi.ptr(ws), wsb, B, N, J, heads, groups, scale, dropout_p, dropout_seed, *TIMER.events("cpb_region1d_bwd", pairs),
-                capi.stream(), capi.deform_opts(ctx.seed_offset)), "deform_attn_region1d_bwd")
-            return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
-        if ctx.multi_head:
-            hg = (heads, groups)
-            wsb = L.smml_deform_attn_region_mh_bwd_workspace_bytes(B, N, J, heads, groups)
-            fn, ev, name, dt = ((L.smml_deform_attn_region_mh_bwd_f32, "cpb_region_mh_bwd", "deform_attn_region_mh_bwd", ()) if m16 is None else
-                                (L.smml_deform_attn16_region_mh_bwd, "cpb16_region_mh_bwd", "deform_attn16_region_mh_bwd", (m16[0],)))
-        else:
-            hg = (heads,)
-            wsb = L.smml_deform_attn_region_bwd_workspace_bytes(B, N, J, heads)
-            fn, ev, name, dt = ((L.smml_deform_attn_region_bwd_f32, "cpb_region_bwd", "deform_attn_region_bwd", ()) if m16 is None else
-                                (L.smml_deform_attn16_region_bwd, "cpb16_region_bwd", "deform_attn16_region_bwd", (m16[0],)))
+        fn, hg, dt, ws_bytes, ws_hg, ev, name = _region_entry(ctx, vs, "bwd")
+        wsb = ws_bytes(B, N, J, *ws_hg)
         ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
-        w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
-        capi.check(fn(*fwd, *w, capi.ptr(tables), capi.fptr(out), capi.fptr(dout), capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits),
-                      *grads, capi.ptr(ws), wsb, B, N, J, *hg, scale, dropout_p, dropout_seed, *dt, *TIMER.events(ev, pairs), capi.stream(),
+        w = () if vs.shape[-1] == 1 else tuple(capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3))
+        capi.check(fn(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), *w, capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
+                      capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits), *grads, capi.ptr(ws), wsb, B, N, J, *hg, scale, dropout_p,
+                      dropout_seed, *dt, *TIMER.events(ev, B * heads * N * J), capi.stream(),
                       capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
         return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
