@@ -29,9 +29,6 @@
 
 namespace {
 
-#ifndef SMML_RGN_EXP
-#define SMML_RGN_EXP 0                   // measurement variants of the region forward (tests/build_variants.py): 1 no cell gather, 2 no record /
-#endif                                   // sub-cell resolution, 3 no score store, 4 no region-id store, 5 no signed logs, 6 no LDS (a, c) read
 constexpr int RG_MAX_KEYS = 16384;       // keys per (bag, head) the region entry points accept
 constexpr int RG_G = 1024;               // level-0 cells per axis
 constexpr int RG_SUB = 8;                // sub-cells per axis of a refined cell
@@ -683,18 +680,10 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float2 vv = *reinterpret_cast<const float2*>(&vsl[buf][acc_row(r, hf)][0]);
-#if SMML_RGN_EXP == 5
-      p0[r] = (gq0 - vv.x) * 0.5f; p1[r] = (gq1 - vv.y) * 0.5f;
-#else
       p0[r] = slog1p(gq0 - vv.x);
       p1[r] = slog1p(gq1 - vv.y);
-#endif
       int cx, cy;
-#if SMML_RGN_EXP == 1
-      ent[r] = region_cell_index(fmaf(p0[r], cs, co), fmaf(p1[r], cs, co), cx, cy) & 1023u;
-#else
       ent[r] = rv.t0[region_cell_index(fmaf(p0[r], cs, co), fmaf(p1[r], cs, co), cx, cy)];
-#endif
     }
   };
   // Step 2a: refined cells (0.7 % of the pairs) take their sub-cell's code, loaded into the cell code's own register (a third of the
@@ -703,7 +692,6 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const unsigned e = ent[r];
-#if SMML_RGN_EXP != 2 && SMML_RGN_EXP != 7
       if (e - RG_E_SUB0 < RG_E_EDGE0 - RG_E_SUB0) {
         // sub-cell of p: the low bits of floor(RG_SUB u) clamped to the grid - the same cell as clamp(floor(RG_SUB (u - cell)), 0, RG_SUB - 1)
         // of the table build (RG_SUB u is exact: a power-of-two multiple; inside the grid u - cell is exact too, outside both clamp to
@@ -712,7 +700,6 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
         const int Y = min(max((int)fmaf(p1[r], cs * (float)RG_SUB, co * (float)RG_SUB), 0), RG_G * RG_SUB - 1);
         ent[r] = rv.t1[(e - RG_E_SUB0) * (RG_SUB * RG_SUB) + (Y & (RG_SUB - 1)) * RG_SUB + (X & (RG_SUB - 1))];
       }
-#endif
     }
   };
   // Step 2b: the records of the one-kink cells (8 % of the pairs) - every lane reads one per pair (record 0 where it needs none: one
@@ -722,11 +709,7 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const unsigned es = ent[4 * g + i] - RG_E_EDGE0;
-#if SMML_RGN_EXP == 8
-      dst[i] = make_float4(__uint_as_float(es), 1.f, 0.5f, __uint_as_float(0x00010002u));
-#else
       dst[i] = rv.edge[es < (unsigned)RG_EDGES ? es : 0u];
-#endif
     }
   };
   step1(0);
@@ -778,23 +761,15 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
       for (int i = 0; i < 4; ++i) {
         const int r = 4 * g + i;
         const unsigned e = ent[r];
-#if SMML_RGN_EXP == 2
-        const unsigned id = e & 1023u;
-#else
         // side of the kink for every lane (record 0 where the code is no record), merged by a bit mask: some lane of the wave needs the
         // record in 99 % of the steps, so a branch around the three multiply-adds never skips them - and the compiler would move the
         // record's load into that branch
         const unsigned em = (e - RG_E_EDGE0) < (unsigned)RG_EDGES ? 0xFFFFFFFFu : 0u;
         const unsigned id = (region_side(rec[g & 1][i], p0[r], p1[r]) & em) | (e & ~em);    // region ids and 0xFFFF pass through
-#endif
         // (a, c) of the region from LDS, no branch.  Ids beyond the LDS-resident regions and "no region" (~1e-4 of the pairs) read some
         // entry and add nothing here; `spec` tells the wave afterwards whether it has such a pair at all
         const bool inl = id < (unsigned)lcap;
-#if SMML_RGN_EXP == 6
-        const float4 ac = make_float4(__uint_as_float(id), 0.5f, 0.25f, 0.f);
-#else
         const float4 ac = regl[id & (unsigned)(RG_LCAP - 1)];
-#endif
         const float bias = fmaf(ac.x, p0[r], fmaf(ac.y, p1[r], ac.z));
         spec |= (!inl && acc_row(r, hf) < nk) ? (1u << r) : 0u;
         ridl[wave][acc_row(r, hf)][c] = (unsigned short)id;
@@ -822,7 +797,7 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
       wave_lds_fence();
       const int key = lane >> 1, qh16 = (lane & 1) * 16;
       const uint4 w0 = *reinterpret_cast<const uint4*>(&ridl[wave][key][qh16]), w1 = *reinterpret_cast<const uint4*>(&ridl[wave][key][qh16 + 8]);
-      if (key < nk && SMML_RGN_EXP != 4) {
+      if (key < nk) {
         uint4* dst = reinterpret_cast<uint4*>(RIDb + (size_t)(j0 + key) * 32 + qh16);
         dst[0] = w0;
         dst[1] = w1;
@@ -870,12 +845,12 @@ __global__ __launch_bounds__(256, 2) void deform_region_fwd_kernel(
       }
       if (nk == KT) {                         // interior tile (uniform): no bounds branches around the stores
 #pragma unroll
-        for (int r = 0; r < 16; ++r) if (SMML_RGN_EXP != 3) LTb[(size_t)(j0 + acc_row(r, hf)) * 32 + c] = s[r];
+        for (int r = 0; r < 16; ++r) LTb[(size_t)(j0 + acc_row(r, hf)) * 32 + c] = s[r];
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = acc_row(r, hf);
-          if (key < nk && SMML_RGN_EXP != 3) LTb[(size_t)(j0 + key) * 32 + c] = s[r];
+          if (key < nk) LTb[(size_t)(j0 + key) * 32 + c] = s[r];
         }
       }
     }

@@ -26,27 +26,10 @@ int smml_deform_attn_nst(int N);
 size_t smml_deform_attn_bwd_workspace_bytes(int B, int N, int J, int H);
 }
 
-// measurement knobs of this file (tests/build_variants.py)
-#ifndef SMML16_FWD_WPS
-#define SMML16_FWD_WPS 2      // waves per SIMD the forward is register-budgeted for
-#endif
-#ifndef SMML16_CPB_WPS
-#define SMML16_CPB_WPS 2      // same, position-bias backward
-#endif
-#ifndef SMML16_FWD_PAIR
-#define SMML16_FWD_PAIR 0     // 1: two keys per trip of the forward's position-bias loop (software pipelining left to the scheduler)
-#endif
-#ifndef SMML16_DP_MFMA
-#define SMML16_DP_MFMA 1      // 1 (default; 0 = the fp32 path's vector form: measurement switch): d p = W1^T (m1 . d h1) of the position-bias backward (the d vs path) as one bf16 product on the matrix pipe (2 MFMAs
-                              // + 8 conversions) instead of 16 packed FMAs + 8 LDS table reads: the kernel is vector-ISSUE bound (PMC: VALU issue
-                              // cycles = kernel time, the matrix pipe 23 % busy), so an MFMA costs one issue slot.  A/B on one box, twice:
-                              // 5.83 -> 5.50 and 5.91 -> 5.59 ms per launch (8 bags of 10 000 x 625 x 8 heads)
-#endif
-#ifndef SMML16_GATE_MUL
-#define SMML16_GATE_MUL 0     // 1: the layer-1 ReLU gate of the backward as an exact 0 / 1 multiplier (clamped multiply) instead of compare + select
-#endif
-
 namespace {
+
+constexpr int FWD16_WPS = 2;      // waves per SIMD the forward is register-budgeted for
+constexpr int CPB16_WPS = 2;      // same, position-bias backward
 
 // ------------------------------------------------------------------------------------------------
 // forward.  One wave = 32 queries on the lane axis (deform_attn.hip's mapping); K / V tiles are converted to T when staged
@@ -63,7 +46,7 @@ struct TabCfg {
 template <int PD, int TG> constexpr int tab_cells() { return TG <= 0 ? 1 : (PD == 2 ? TG * TG : TG); }
 
 template <int PDX, bool SAVE, typename T, int TG = 0>
-__global__ __launch_bounds__(256, SMML16_FWD_WPS) void deform16_fwd_kernel(
+__global__ __launch_bounds__(256, FWD16_WPS) void deform16_fwd_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, const float* __restrict__ VS,
     const float* __restrict__ GQ, CpbParams cp, float* __restrict__ O, float* __restrict__ LSE, u16* __restrict__ LT,
     u16* __restrict__ MK, int N, int J, int H, int G, int NST, float scale, DropCfg dc_in, TabCfg tc = TabCfg{}) {
@@ -183,10 +166,8 @@ __global__ __launch_bounds__(256, SMML16_FWD_WPS) void deform16_fwd_kernel(
 
     // continuous position bias: layer 1 (fp32-grade, deform_common.h) + one T-term layer 2 per key
     const int nk = min(KT, J - j0);
-    // one key's chain: layer 1 (MFMA) -> ReLU, T -> layer 2 (two dependent MFMAs) -> ReLU, layer 3, mask bits.  SMML16_FWD_PAIR runs two
-    // keys per trip so that the scheduler can fill one chain's MFMA latencies with the other's vector work (padded keys of a ragged tile
-    // compute on zero positions; only their mask store is guarded)
-    auto bias_chain = [&](int jj, bool store_mask) {
+    // one key's chain: layer 1 (MFMA) -> ReLU, T -> layer 2 (two dependent MFMAs) -> ReLU, layer 3, mask bits
+    auto bias_chain = [&](int jj) {
       const float p0 = pos_of<RAW>(gq0 - vsl[buf][jj][0]);
       const float p1 = (PD == 2) ? slog1p(gq1 - vsl[buf][jj][1]) : 0.f;
       floatx16 d = b2acc;
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(256, SMML16_FWD_WPS) void deform16_fwd_kernel(
           mb3 = fmaf(fminf(fmaxf(rb[1] * big, 0.f), 1.f), (float)(1u << ((16 + r) & 15)), mb3);
         }
       }
-      if (SAVE && store_mask) MKb[(size_t)(j0 + jj) * 64 + c] = (u16)(unsigned)((mb0 + mb1) + (mb2 + mb3));   // rows of padded query lanes exist
+      if (SAVE) MKb[(size_t)(j0 + jj) * 64 + c] = (u16)(unsigned)((mb0 + mb1) + (mb2 + mb3));   // rows of padded query lanes exist
       ta += tb;
       biasT[wave][jj][c] = xhalf_sum(ta[0] + ta[1]);
     };
@@ -239,14 +220,7 @@ __global__ __launch_bounds__(256, SMML16_FWD_WPS) void deform16_fwd_kernel(
         }
       }
     } else {
-#if SMML16_FWD_PAIR
-      for (int jj = 0; jj < nk; jj += 2) {
-        bias_chain(jj, true);
-        bias_chain(jj + 1, jj + 1 < nk);          // jj + 1 <= 31: inside the staged tile
-      }
-#else
-      for (int jj = 0; jj < nk; ++jj) bias_chain(jj, true);
-#endif
+      for (int jj = 0; jj < nk; ++jj) bias_chain(jj);
     }
     wave_lds_fence();
 
@@ -401,11 +375,7 @@ __global__ __launch_bounds__(256, 2) void deform16_bwd_dq_kernel(
     }
   }
   delta = xhalf_sum(delta);                             // of the scaled row: dP below is scaled alike
-#if SMML_FAST_MATH
   const float nl = prob_bias(LSE[(size_t)(b * H + h) * N + qi]) + (float)e2;                       // P 2^e = exp2(l log2e - lse log2e + e)
-#else
-  const float nl = prob_bias(LSE[(size_t)(b * H + h) * N + qi]) + (float)e2 * 0.6931471805599453f;
-#endif
 
   floatx16 dq0 = {0}, dq1 = {0};
   const float* Kb = K + (size_t)b * J * HD + h * DH;
@@ -649,7 +619,7 @@ struct MaskTab {
   float invh, off, imax;   // cell index along an axis = clamp(p * invh + off, 0, imax) truncated
 };
 template <int PDX, int MSRC = 0, bool EXPORT = false>
-__global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
+__global__ __launch_bounds__(256, CPB16_WPS) void cpb16_bwd_kernel(
     const u16* __restrict__ dLT, const u16* __restrict__ MK, const float* __restrict__ VS, const float* __restrict__ GQ,
     CpbParams cp, float* __restrict__ slab, float* __restrict__ dvs_slab, int N, int J, int H, int G, int NST, u16* __restrict__ MKO = nullptr,
     MaskTab mt = MaskTab{}) {
@@ -675,7 +645,7 @@ __global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
     const int ch = acc_row(tid & 15, tid >> 4);
     if (RECOMP) {                                           // 2 b2 of the half's 16 output rows (the chain runs on 2 h1 = relu2)
       tab[(tid >> 4) * 32 + (tid & 15)] = 2.f * cp.b2[ch];
-    } else {
+    } else {                                                // written, not read since d p = W1^T (m1 . d h1) moved to the matrix pipe
       tab[(tid >> 4) * 32 + (tid & 15)] = cp.w1[ch * PD];
       tab[(tid >> 4) * 32 + 16 + (tid & 15)] = (PD == 2) ? cp.w1[ch * PD + 1] : 0.f;
     }
@@ -736,7 +706,6 @@ __global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
       w2f[kb] = cvt8<__bf16>(wv);
     }
   }
-#if SMML16_DP_MFMA
   bf16x8 a1d[2];                       // W1^T as an A operand: row 0 = w1x, row 1 = w1y over k = hidden channel acc_row(8 kb + j, hf); other rows zero
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb)
@@ -746,7 +715,6 @@ __global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
       const float wv = (c == 0) ? cp.w1[ch * PD] : ((c == 1 && PD == 2) ? cp.w1[ch * PD + 1] : 0.f);
       a1d[kb][j] = (__bf16)wv;
     }
-#endif
   float big;
   asm("s_mov_b32 %0, 0x71800000" : "=s"(big));
   floatx16 e = {0};                    // sum_q mask[out, q] g[in, q]: rows = out, lane = in (times w3[out] at the end)
@@ -817,15 +785,9 @@ __global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
       const uint4v tw = {pt.hw, pt.mw, hf ? pt.hw : pt.lw, hf ? 0x00003F80u : 0x3F803F80u};
       ht = mfma16b(__builtin_bit_cast(bf16x8, tw), a1t, (floatx16){0});
     }
-#if SMML16_GATE_MUL
-    float on1[16];                      // exact 0.0 / 1.0: clamp(x 2^100)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) on1[r] = fminf(fmaxf(xacc[r] * big, 0.f), 1.f);
-#else
     bool on1[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) on1[r] = xacc[r] > 0.f;
-#endif
 
     half8 mk[2];
     if constexpr (RECOMP) {
@@ -913,39 +875,22 @@ __global__ __launch_bounds__(256, SMML16_CPB_WPS) void cpb16_bwd_kernel(
       float2v dp0v = {0.f, 0.f}, dp1v = {0.f, 0.f};
       const float dbl = dbias * unlift2;
       const float p0i = p0 * dbl, p1i = p1 * dbl;
-#if SMML16_DP_MFMA
       uint4v xw0, xw1;
-#endif
 #pragma unroll
       for (int p = 0; p < 8; ++p) {
         float2v g1;
-#if SMML16_GATE_MUL
-        g1 = (float2v){dh[2 * p], dh[2 * p + 1]} * (float2v){on1[2 * p], on1[2 * p + 1]};
-#else
         g1[0] = on1[2 * p] ? dh[2 * p] : 0.f;
         g1[1] = on1[2 * p + 1] ? dh[2 * p + 1] : 0.f;
-#endif
         ab1[p] = g1 * (float2v){dbl, dbl} + ab1[p];
         aw1x[p] = g1 * (float2v){p0i, p0i} + aw1x[p];
         if (PD == 2) aw1y[p] = g1 * (float2v){p1i, p1i} + aw1y[p];
-#if SMML16_DP_MFMA
         if (p < 4) xw0[p] = pack2<__bf16>(g1[0], g1[1]); else xw1[p - 4] = pack2<__bf16>(g1[0], g1[1]);
-#else
-        const float2 wx = *reinterpret_cast<const float2*>(tabh + 2 * p);
-        dp0v = g1 * (float2v){wx.x, wx.y} + dp0v;
-        if (PD == 2) {
-          const float2 wy = *reinterpret_cast<const float2*>(tabh + 16 + 2 * p);
-          dp1v = g1 * (float2v){wy.x, wy.y} + dp1v;
-        }
-#endif
       }
-#if SMML16_DP_MFMA
       // d p[c][query] = sum_ch W1[ch][c] (m1 . d h1)[ch][query]: rows 0 / 1 of the product = registers 0 / 1 of the lanes of half 0 (complete sums:
       // the K dimension covers all 32 channels); half 1 holds rows 4 / 5 = 0
       floatx16 dpa = mfma16b(a1d[0], __builtin_bit_cast(bf16x8, xw0), (floatx16){0});
       dpa = mfma16b(a1d[1], __builtin_bit_cast(bf16x8, xw1), dpa);
       dp0v[0] = dpa[0]; dp1v[0] = dpa[1];
-#endif
       float2 v;
       v.x = -(dp0v[0] + dp0v[1]) * dbl * dpos_of<RAW>(d0, big);
       v.y = (PD == 2) ? -(dp1v[0] + dp1v[1]) * dbl * (srcp(fabsf(d1) + 1.f) * fminf(fmaxf(fabsf(d1) * big, 0.f), 1.f)) : 0.f;

@@ -1,105 +1,20 @@
 // Shared pieces of the fused deformable cross-attention kernels (deform_attn.hip: fp32-grade split products; deform_attn16.hip:
-// the 16-bit compute mode): tuning knobs, fast-math helpers, the counter-based dropout mask, layer 1 of the position-bias MLP on
+// the 16-bit compute mode): fast-math helpers, the counter-based dropout mask, layer 1 of the position-bias MLP on
 // the matrix pipe (one device function for the forward, the backward and the decision export of BOTH modes, so their layer-1 ReLU
 // decisions are the same bits), the fixed-order slab reducers and the workspace layout of the backward.
 // Reference: models/DeformableAttention2D.py:120-157,284-312; models/DeformableAttention1D.py:60-102,205-232.
 #pragma once
 #include "smml_common.h"
 
-// tuning knobs (defaults = the configuration measured fastest on MI355X; tests/microbench sweeps them)
-#ifndef SMML_FWD_WPS
-#define SMML_FWD_WPS 2      // waves per SIMD the forward kernel is register-budgeted for
-#endif
-#ifndef SMML_SPLIT_TERMS
-#define SMML_SPLIT_TERMS 3    // products kept of W h = (wh + wm + wl)(hh + hl) in the 32x32 layer of the forward:
-                              //   3 = wh hh + wh hl + wm hh (<= 2^-21 |w||h| dropped), 4 adds wm hl (W2 and h both to 22 bits: <= 2^-23
-                              //   dropped), 5 adds wl hh (W2 to 33 bits).  The layer's VALUE is fp32-grade with 3; its SIGN is the ReLU mask the
-                              //   backward consumes, and with 3 terms a few more rounding-level ties (|pre-activation| ~ 1e-7) fall the other
-                              //   way than in an fp64 evaluation (profiles/r02_split_terms.txt: 8-9 of 2.3e8 decisions for every variant,
-                              //   torch fp32: 6).  Round 2 shipped 4 terms because its gradient-level gate compared gradients ACROSS such
-                              //   flips (one flipped unit moves dW1 by ~4e-4 of its norm); round 3's parity tests impose the kernels' own
-                              //   decisions on the oracle (tests/helpers.py), under which 3 and 4 terms give the same errors
-                              //   (gpurun_out/parity_report_{default,s3}.tsv) - and 3 is two MFMAs per key cheaper (-0.5 ms per 8-bag step).
-#endif
-#ifndef SMML_DELTA_FIX
-#define SMML_DELTA_FIX 0      // 1: re-centre the rows of d bias in the position-bias backward (d bias_k - P_k sum_k d bias_k).
-                              // A fused softmax backward leaves sum_k dS_k != 0 at the 1e-7 level (delta = rowsum(dO . O));
-                              // sums that weight d bias with near-constant factors amplify it.  Measured (tests/diag_gterms.py):
-                              // dW3 4x and, with every ReLU unit active, dW2 / db 3-4x closer to fp64; everything else
-                              // unchanged; costs 0.3-0.45 ms of the 17.5 ms step (one more score read + an exp per pair).
-#endif
-#ifndef SMML_FWD_PAIR
-#define SMML_FWD_PAIR 0       // 1: two keys per trip of the forward's position-bias loop (measurement variant)
-#endif
-#ifndef SMML_DELTA_EXACT
-#define SMML_DELTA_EXACT 0    // 1: the dq pass forms delta = sum_k P_k dP_k from its own dP products in a first sweep over the keys (measurement
-                              // variant, deform_attn.hip; + ~0.4 ms per 8-bag step).  Default: delta = rowsum(dO . O).
-#endif
-#ifndef SMML_CHAIN2_TERMS
-#define SMML_CHAIN2_TERMS 2   // fp16 terms of the constant (W2 w3)^T in d h1 = (W2 w3)^T mask.  The mask operand is exact, so the
-                              // only error is the constant's: 2 terms = 22 bits, a fixed relative perturbation <= 2^-23 of
-                              // each (W2 w3)[out][in] - below what rounding d bias w3 and the 32-term fp32 dot cost the
-                              // unfused evaluation.  3: the constant to 2^-33.
-#endif
-#ifndef SMML_G_TERMS
-#define SMML_G_TERMS 2        // bf16 terms of g = h1 . d bias in the dW2 product of the position-bias backward.  2: every
-                              // summand carries 16 mantissa bits (<= 2^-17 relative, round-to-nearest, unbiased) against an
-                              // exact 0 / 1 mask operand, fp32 accumulation - the error of dW2 against an fp64 evaluation
-                              // is unchanged to three digits vs 3 terms (tests/diag_gterms.py: it is set by ReLU mask flips
-                              // and by delta = rowsum(dO . O)), and the kernel is 10 % faster.  3: fp32-grade summands.
-#endif
-#ifndef SMML_BWD_EXP
-#define SMML_BWD_EXP 0        // measurement variants of the dq / dkv passes (wrong results): 1 no dP products, 2 no dQ products, 3 no dK / dV products
-#endif
-#ifndef SMML_BWD_TERMS
-#define SMML_BWD_TERMS 3      // bf16 terms per operand in the dq pass: 3 = fp32-grade (six products per block), 2 = 16-bit operands (hi + mid,
-                              // three products: measurement switch - d scores then carry 2^-17 errors, which the position-bias gradients
-                              // (dW3) and the single-key case (dS = 0 exactly) do not pass the parity gate with, profiles/r02_split_terms.txt)
-#endif
-#ifndef SMML_DQ_OUT_TERMS
-#define SMML_DQ_OUT_TERMS 2   // the dQ = dS K product of the dq pass (a plain output, like dK / dV): two terms; the d scores themselves
-                              // (dP = V dO^T, SMML_BWD_TERMS) keep three
-#endif
-#ifndef SMML_DKV_TERMS
-#define SMML_DKV_TERMS 2      // the dkv pass: hi + mid bf16 terms (16 operand bits, three products).  dK and dV are plain sums of products -
-                              // nothing downstream recomputes from them, unlike the d scores of the dq pass - and land 6e-6 from fp64
-                              // (l2; fp32 operands: 5e-7), inside the 1e-4 gate of every parity test; once the dropout hashes were out
-                              // of the pass (r03) the third term's 24 MFMAs per tile were its longest pole: -0.33 ms per 8-bag step, A/B
-                              // on one box.  3 = fp32-grade operands.
-#endif
-#ifndef SMML_FWD_QK16
-#define SMML_FWD_QK16 1       // forward QK^T / PV on the 16-bit matrix pipe: every operand as fp16 hi + lo (RNE, 22 bits), three of the
-                              // four cross products (hi hi, hi lo, lo hi; <= 2^-22 dropped) - 24 MFMAs of 32 cycles per 32-key tile
-                              // instead of 64 fp32 MFMAs of 64 cycles (which run at the vector rate and share the ALUs).  0: fp32 MFMA.
-#endif
-#ifndef SMML_FMA_MIX
-#define SMML_FMA_MIX 1          // residual of the fp16 split by v_fma_mix_f32 (one instruction per value instead of convert + subtract)
-#endif
-#ifndef SMML_FAST_MATH
-#define SMML_FAST_MATH 1    // 1: hardware log2/exp2/rcp approximations (1 ulp) instead of the libm-accurate forms
-#endif
-
 namespace {
 
-#if SMML_FAST_MATH
+// log, exp and reciprocal are the hardware approximations (v_log_f32, v_exp_f32, v_rcp_f32: 1 ulp), not the libm forms.
 // |d| + 1 >= 1 is never subnormal: the raw v_log_f32 (log2) needs none of __logf's range handling
-#ifndef SMML_RAW_LOG
-#define SMML_RAW_LOG 1
-#endif
 __device__ __forceinline__ float slog1p(float d) {
-#if SMML_RAW_LOG
   return copysignf(__builtin_amdgcn_logf(fabsf(d) + 1.0f) * 0.6931471805599453f, d);
-#else
-  return copysignf(__logf(fabsf(d) + 1.0f), d);
-#endif
 }
 __device__ __forceinline__ float sexp(float x) { return __expf(x); }
 __device__ __forceinline__ float srcp(float x) { return __builtin_amdgcn_rcpf(x); }
-#else
-__device__ __forceinline__ float slog1p(float d) { return signed_log1p(d); }
-__device__ __forceinline__ float sexp(float x) { return expf(x); }
-__device__ __forceinline__ float srcp(float x) { return 1.0f / x; }
-#endif
 // 2 relu(x) = x + |x|, exact.  On gfx950 v_add_f32 (with its free |.| modifier) is in the fast issue class (~1.1 ns per
 // instruction per SIMD with two resident waves) while v_max_f32 is in the slow one (~2.0 ns) -
 // tests/microbench/valu_mix_probe.hip; the factor 2 is folded into the constants downstream (powers of two: exact).
@@ -137,15 +52,11 @@ __device__ __forceinline__ void split8(const float (&x)[8], half8& hi, half8& lo
   for (int i = 0; i < 4; ++i) {
     const float2v v = {x[2 * i], x[2 * i + 1]};
     const half2v h = __builtin_convertvector(v, half2v);
-#if SMML_FMA_MIX
     // x - float(hi) in one mixed-precision fma per value (v_fma_mix_f32 reads the fp16 half directly)
     const unsigned hp = __builtin_bit_cast(unsigned, h);
     float2v r;
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r[0]) : "v"(hp), "v"(v[0]));
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r[1]) : "v"(hp), "v"(v[1]));
-#else
-    const float2v r = {x[2 * i] - (float)h[0], x[2 * i + 1] - (float)h[1]};
-#endif
     const half2v l = __builtin_convertvector(r, half2v);
     hi[2 * i] = h[0]; hi[2 * i + 1] = h[1];
     lo[2 * i] = l[0]; lo[2 * i + 1] = l[1];
@@ -184,14 +95,12 @@ __device__ __forceinline__ half8 lds_frag_tr_h(const _Float16* p0, const _Float1
 constexpr int FRLD = 64 + 8;    // halves per row of a row-read fp16 image (144-byte rows)
 constexpr int FTLD = 64 + 32;   // halves per row of a transposed-read fp16 image (192-byte rows)
 
-// D += W . h with W = wh + wm + wl (exact) and h = bh + bl: all products down to 2^-22 of the leading one
-__device__ __forceinline__ floatx16 mfma16_split(half8 wh, half8 wm, half8 wl, half8 bh, half8 bl, floatx16 d) {
-#if SMML_SPLIT_TERMS == 5
-  d = mfma16(wl, bh, d);
-#endif
-#if SMML_SPLIT_TERMS >= 4
-  d = mfma16(wm, bl, d);        // 4: W2 to 22 bits (hi + mid; <= 2^-23 |w| dropped, below fp32's own product rounding), h to 22 bits
-#endif
+// D += W . h with W = wh + wm (22 bits) and h = bh + bl: the three products wh bh + wh bl + wm bh (<= 2^-21 |w||h| dropped).  The
+// layer's VALUE is fp32-grade with three; its SIGN is the ReLU mask the backward consumes, and a fourth (wm bl) or fifth (wl bh)
+// product changes neither the number of rounding-level ties (|pre-activation| ~ 1e-7) that fall the other way than in an fp64
+// evaluation (8-9 of 2.3e8 decisions, torch fp32: 6; profiles/r02_split_terms.txt) nor any error of the parity tests, which impose
+// the kernels' own decisions on the oracle (tests/helpers.py) - at two more MFMAs per key.
+__device__ __forceinline__ floatx16 mfma16_split(half8 wh, half8 wm, half8 bh, half8 bl, floatx16 d) {
   d = mfma16(wm, bh, d);
   d = mfma16(wh, bl, d);
   return mfma16(wh, bh, d);
@@ -277,22 +186,17 @@ __device__ __forceinline__ float wave_max_all(float v) {
 // while the residual terms stay NORMAL fp16 numbers (>= 2^-14); for weights of size 0.01 .. 0.1 the second term is already
 // subnormal (spacing 2^-24 absolute) and the split degrades to ~2^-20 relative.  Scaling the whole operand by 2^k so that its
 // largest element sits near `target` (a power of two; exact) keeps every kept term normal; the consumer undoes the scale.
-#ifndef SMML_LIFT_FWD
-#define SMML_LIFT_FWD 0       // lift of W2 in the forward's layer-2 product.  OFF: measured (profiles/r02_split_terms.txt) it makes the saved
-                              // ReLU masks flip MORE often against fp64 (dW1 1.06e-3 instead of 2.07e-4 with 5 terms) although every
-                              // term is more precise - not understood; the reference's init (N(0, 1/sqrt(32)) = 0.18) keeps the second
-                              // term of the unlifted split normal anyway
-#endif
-#ifndef SMML_LIFT_BWD
-#define SMML_LIFT_BWD 1       // lift of the chain-2 constants (W2 w3)^T in the backward: d vs 90 x closer to fp64 when every unit is active
-#endif
 __device__ __forceinline__ float pow2_lift(float amax, float target, float lo, float hi) {
   if (!(amax > 0.f)) return 1.f;
   const float k = floorf(log2f(target / amax));
   return ldexpf(1.f, (int)fminf(fmaxf(k, lo), hi));      // an exact power of two (exp2f is the 1-ulp hardware approximation)
 }
 
-// one 32x32x16 block of a backward contraction from split operands (TERMS bf16 terms per operand: 3 = six products, 2 = three)
+// one 32x32x16 block of a backward contraction from split operands (TERMS bf16 terms per operand: 3 = six products, fp32-grade;
+// 2 = three products of 16-bit operands, al / bl not read).  The d scores (dP = V dO^T) take 3: the position-bias gradients and the
+// softmax backward recompute from them, and with 2^-17 errors dW3 and the single-key case (dS = 0 exactly) miss the parity gate
+// (profiles/r02_split_terms.txt).  dQ, dK, dV take 2: plain sums of products that nothing downstream recomputes from; they land
+// 6e-6 from fp64 (l2; fp32-grade operands: 5e-7) inside the 1e-4 gate, and the third term's MFMAs were the passes' longest pole.
 template <int TERMS>
 __device__ __forceinline__ floatx16 bwd_prod(bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh, bf16x8 bm, bf16x8 bl, floatx16 d) {
   if (TERMS == 3) return mfma16b_x6(ah, am, al, bh, bm, bl, d);
@@ -340,14 +244,9 @@ constexpr int VBLD = DH + 8;    // halves per row of a V plane
 constexpr int KBLD = DH + 32;   // halves per row of a K plane
 constexpr float LOG2E = 1.4426950408889634f;
 
-#if SMML_FAST_MATH
 // exp(l - lse) as one fma + v_exp_f32: nl = -lse * log2(e)
 __device__ __forceinline__ float prob_of(float l, float nl) { return __builtin_amdgcn_exp2f(fmaf(l, LOG2E, nl)); }
 __device__ __forceinline__ float prob_bias(float lse) { return -lse * LOG2E; }
-#else
-__device__ __forceinline__ float prob_of(float l, float nl) { return expf(l + nl); }
-__device__ __forceinline__ float prob_bias(float lse) { return -lse; }
-#endif
 
 constexpr int QBLD = DH + 32;  // halves per row of a Q / dO plane: 192-byte rows (four rows of a transposed read on disjoint banks)
 constexpr int DKV_KEYS = KT * WAVES;
@@ -486,7 +385,7 @@ static BwdWorkspace bwd_workspace(int B, int N, int J, int H) {
   w.partial = nwg * CPB_SLAB;
   w.dkp = (w.partial + (size_t)CPB_RED_CHUNKS * CPB_SLAB * 2 + 3) & ~(size_t)3;
   w.dvp = w.dkp + kv;
-  w.rho = w.dvp + kv;                      // [B, H, N] row sums of d scores (SMML_DELTA_FIX)
+  w.rho = w.dvp + kv;                      // [B, H, N] row sums of d scores: written by the dq pass, not read since the re-centring of d bias was retired
   w.dvs = w.rho + (((size_t)B * H * N + 3) & ~(size_t)3);     // [nwg * WAVES][J][2] d vs rows of the position-bias backward
   w.total = w.dvs + nwg * WAVES * (size_t)J * 2;
   return w;

@@ -38,11 +38,9 @@ struct B16Args {
   long long sa, sb, sc;          // batch strides in elements (gridDim.z problems; sc = 0 with split-K: the batches add up in one output)
 };
 
-#ifndef SMML_B16_MINBLOCKS
-#define SMML_B16_MINBLOCKS 2
-#endif
+constexpr int B16_MINBLOCKS = 2;      // waves per SIMD (workgroups of 256 per CU) the kernel is register-budgeted for
 template <bool TN, bool OUT_BF16>
-__global__ __launch_bounds__(256, SMML_B16_MINBLOCKS) void gemm_b16_kernel(B16Args g) {
+__global__ __launch_bounds__(256, B16_MINBLOCKS) void gemm_b16_kernel(B16Args g) {
   constexpr int PLANE = TN ? RC_PLANE : KC_PLANE;
   __shared__ __attribute__((aligned(16))) __bf16 smem[2 * PLANE];
   __bf16* As = smem;

@@ -81,28 +81,13 @@ __device__ __forceinline__ floatx16 mfma16b_x6(bf16x8 ah, bf16x8 am, bf16x8 al, 
   d = mfma16b(ah, bm, d);
   return mfma16b(ah, bh, d);
 }
-// four fp32 -> three planes of four bf16 (8 bytes each)
-#ifndef SMML_DOT2_SPLIT
-#define SMML_DOT2_SPLIT 0   // exact but not faster: fewer instructions, yet every DOT result costs 3 wait states (tests/microbench/README.md)
-#endif
-// v - float(h) for a packed bf16 pair h = rn(v): exact (the residual of a rounding fits fp32).  v_dot2_f32_bf16 against
-// the constant pairs {-1, 0} / {0, -1} reads the packed halves directly - one instruction per value instead of unpacking
-// (shift / and) and subtracting; exactness incl. subnormals checked by tests/microbench/dot2_probe.hip.  Through the
-// builtin, never inline asm: a DOT result needs 3 wait states before another VALU instruction reads it, which only the
-// compiler's hazard recognizer inserts.
+// v - float(h) for a packed bf16 pair h = rn(v): exact (the residual of a rounding fits fp32).  Unpack and subtract: v_dot2_f32_bf16
+// against the constant pairs {-1, 0} / {0, -1} is exact too and one instruction per value, but every DOT result costs 3 wait
+// states - not faster (tests/microbench/README.md, dot2_probe.hip).
 __device__ __forceinline__ float2v bf16_residual2(const float2v v, const bf16x2 h) {
-#if SMML_DOT2_SPLIT
-  // the constant pairs are kept opaque in VGPRs: folded to an inline constant, {-1, 0} is encoded as "-1.0", which
-  // the instruction does not read as a bf16 pair (dot2_probe.hip caught it)
-  unsigned c0, c1;
-  asm("v_mov_b32 %0, 0x0000bf80" : "=v"(c0));
-  asm("v_mov_b32 %0, 0xbf800000" : "=v"(c1));
-  return (float2v){__builtin_amdgcn_fdot2_f32_bf16(h, __builtin_bit_cast(bf16x2, c0), v[0], false),
-                   __builtin_amdgcn_fdot2_f32_bf16(h, __builtin_bit_cast(bf16x2, c1), v[1], false)};
-#else
   return (float2v){v[0] - (float)h[0], v[1] - (float)h[1]};
-#endif
 }
+// four fp32 -> three planes of four bf16 (8 bytes each)
 __device__ __forceinline__ void split4_bf3(const float4 v, uint2v& h, uint2v& m, uint2v& l) {
   const float2v a = {v.x, v.y}, b = {v.z, v.w};
   const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
@@ -133,9 +118,7 @@ __device__ __forceinline__ bf16x8 lds_frag_tr(const __bf16* p0, const __bf16* p1
   return (bf16x8){r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
 }
 
-#ifndef SMML_DPP_REDUCE
-#define SMML_DPP_REDUCE 1   // cross-lane sums on the VALU (v_permlane32_swap / DPP) instead of ds_bpermute through LDS
-#endif
+// cross-lane sums stay on the VALU (v_permlane32_swap / DPP), not ds_bpermute through LDS.
 // value of the other 32-lane half: v_permlane32_swap exchanges the upper half of its first operand with the
 // lower half of its second, so with both operands = v the two results hold {lo, lo} and {hi, hi}
 __device__ __forceinline__ void xhalf_pair(float v, float& lo, float& hi) {
@@ -144,7 +127,6 @@ __device__ __forceinline__ void xhalf_pair(float v, float& lo, float& hi) {
   lo = __uint_as_float(r[0]);
   hi = __uint_as_float(r[1]);
 }
-#if SMML_DPP_REDUCE
 __device__ __forceinline__ float xhalf_sum(float v) { float a, b; xhalf_pair(v, a, b); return a + b; }
 __device__ __forceinline__ float xhalf_max(float v) { float a, b; xhalf_pair(v, a, b); return fmaxf(a, b); }
 // sum over the 64 lanes, valid in EVERY lane: inclusive row scan with DPP row_shr 1/2/4/8 (lane 15 of each
@@ -158,15 +140,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   return __uint_as_float(__builtin_amdgcn_readlane(u, 15)) + __uint_as_float(__builtin_amdgcn_readlane(u, 31)) +
          __uint_as_float(__builtin_amdgcn_readlane(u, 47)) + __uint_as_float(__builtin_amdgcn_readlane(u, 63));
 }
-#else
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32); }
-__device__ __forceinline__ float xhalf_max(float v) { return fmaxf(v, __shfl_xor(v, 32)); }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-#endif
 // wave-local ordering of LDS traffic: LDS ops of one wave complete in issue order; this only
 // stops the compiler from moving accesses across the point.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -174,5 +147,3 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// sign(d) * log(|d| + 1)  (continuous position bias input transform)
-__device__ __forceinline__ float signed_log1p(float d) { return copysignf(logf(fabsf(d) + 1.0f), d); }

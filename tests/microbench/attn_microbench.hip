@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
   for (int it = 0; it < reps + 1; ++it) {
     hipEventRecord(e0, 0);
     int rc = smml_deform_attn_fwd_f32(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, lt, mk, B, N, J, H, G, PD, scale,
-                                      drop_p, 77ull, nullptr, nullptr, nullptr);
+                                      drop_p, 77ull, nullptr, nullptr, nullptr, nullptr);      // no events, default stream, default opts
     hipEventRecord(e1, 0);
     if (rc) { printf("fwd error: %s\n", smml_last_error()); return 1; }
     hipEventSynchronize(e1);
@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     if (it > 0) fwd_ms += ms;
     hipEventRecord(e0, 0);
     rc = smml_deform_attn_bwd_f32(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, dout, lse, lt, mk, dlt, dq, dk, dv, dvs, dw1,
-                                  db1, dw2, db2, dw3, db3, ws, wsb, B, N, J, H, G, PD, scale, drop_p, 77ull, c0, c1, nullptr);
+                                  db1, dw2, db2, dw3, db3, ws, wsb, B, N, J, H, G, PD, scale, drop_p, 77ull, c0, c1, nullptr, nullptr);
     hipEventRecord(e1, 0);
     if (rc) { printf("bwd error: %s\n", smml_last_error()); return 1; }
     hipEventSynchronize(e1);

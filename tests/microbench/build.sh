@@ -1,5 +1,6 @@
 #!/bin/bash
-# builds one microbench binary per variant into tests/microbench/bin/ (git-ignored, travels with gpurun)
+# builds the attention harness into tests/microbench/bin/ (git-ignored).  The kernels have one code path: a binary per VARIANT name
+# is only useful to time two source trees side by side
 set -e
 cd "$(dirname "$0")"
 mkdir -p bin && rm -f bin/mb_*
@@ -8,6 +9,5 @@ build() { # name, flags...
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -fno-honor-nans -mno-amdgpu-ieee -fno-slp-vectorize -DVARIANT="\"$name\"" "$@" attn_microbench.hip -o bin/mb_$name &
 }
 build base
-build deltafix -DSMML_DELTA_FIX=1
-wait
+wait %1      # the compiler's exit status (set -e)
 ls bin

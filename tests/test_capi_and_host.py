@@ -35,6 +35,22 @@ def test_library_exports_every_declared_symbol():
     assert len(tl) == 1 and "g_err" in tl[0], tl
 
 
+def test_kernels_have_no_compile_time_switches():
+    """One code path per kernel: no preprocessor conditional of csrc/ names an SMML* macro (a -D measurement variant; the retired ones are
+    listed in HISTORY.md) - only the include guard of the SmmlDeformOpts struct, which smml_common.h shares with include/smml.h."""
+    csrc = os.path.join(ROOT, "subspace-multimodal-learning_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) >= 15
+    found = []
+    for f in files:
+        txt = open(os.path.join(csrc, f)).read().replace("\\\n", " ")       # continued lines belong to their directive
+        for line in txt.split("\n"):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                found += [f"{f}: {line.strip()}" for name in re.findall(r"\bSMML\w*", m.group(2)) if name != "SMML_DEFORM_OPTS_DEFINED"]
+    assert not found, "\n".join(found)
+
+
 def test_argument_counts_match_header():
     txt = open(os.path.join(ROOT, "include", "smml.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)

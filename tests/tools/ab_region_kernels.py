@@ -1,6 +1,6 @@
 """Interleaved A/B of builds of the library on the region forward / backward entry points at the headline shape (8 bags x 8 heads x
 10 000 queries x 625 keys, dropout 0.1): every build named on the command line ("default" = lib/libsmml_hip.so, otherwise
-lib/variants/<name>.so from tests/tools/build_variants.py) is loaded into THIS process and called in turn, round after round, on the same
+lib/variants/<name>.so, e.g. the library built from another revision of the tree) is loaded into THIS process and called in turn, round after round, on the same
 tensors, so that clock / thermal drift of the box hits all of them alike (single runs of bench.py differ by +-5 % on one box).
 Prints the median and the minimum per build: whole forward call, whole backward call (HIP events around the C call).
 usage: python tests/tools/ab_region_kernels.py default v_a v_b [--rounds 12]"""

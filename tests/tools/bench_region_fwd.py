@@ -1,5 +1,6 @@
 """Times the region forward kernel alone at the headline shape (8 bags x 8 heads x 10 000 queries x 625 keys), training mode (scores and
-region ids saved) and inference mode; SMML_LIB selects a measurement variant (tests/tools/build_variants.py, -DSMML_RGN_EXP=k)."""
+region ids saved) and inference mode; SMML_LIB selects another build of the library (e.g. one built from another revision).  The -DSMML_RGN_EXP=k variants
+of profiles/r05_fwd_variants.txt are retired (HISTORY.md, "Retired compile-time switches")."""
 import os, sys, importlib, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,6 @@
 """Diagnostic (not a test): l2 errors of the position-bias gradients of the fused attention core against a torch fp64
-evaluation, next to the errors of the same evaluation in fp32 - run once per library build to compare SMML_G_TERMS = 3 / 2.
+evaluation, next to the errors of the same evaluation in fp32 - run once per library build (SMML_LIB) to compare two of them; it
+measured the two bf16 terms of g against three before that choice was hard-wired (cpb_bwd_kernel).
 Usage on the GPU box:  python tests/tools/diag_gterms.py [N J]"""
 import importlib
 import sys

@@ -1,5 +1,5 @@
 """Instruction mix of the loops that contain MFMAs, per kernel of one HIP source (gfx950 assembly, the flags of _build.py).
-Usage: python tests/tools/isa_loops.py deform_attn.hip [kernel-name-substring] [-DSMML_... flags]"""
+Usage: python tests/tools/isa_loops.py deform_attn.hip [kernel-name-substring] [extra compiler flags]"""
 import collections, importlib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

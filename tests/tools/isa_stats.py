@@ -1,6 +1,7 @@
 """Instruction statistics of the kernels of one HIP source: compiles csrc/<file> to gfx950 assembly with the flags of _build.py
 and prints, per kernel, VGPR count, scratch, and the instruction mix of the whole body and of its hottest loop (the innermost
-loop with the most MFMAs).  Usage: python tests/tools/isa_stats.py deform_attn.hip [-DSMML_SPLIT_TERMS=3 ...]"""
+loop with the most MFMAs).  Usage: python tests/tools/isa_stats.py deform_attn.hip [extra compiler flags]
+(tests/tools/isa_diff.py compares every kernel with a git revision's)."""
 import importlib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
