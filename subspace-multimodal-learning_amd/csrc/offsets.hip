@@ -26,6 +26,19 @@ __device__ __forceinline__ float normalize_pos(float vg, int den) {
   return __fsub_rn(__fdiv_rn(__fmul_rn(2.f, vg), (float)den), 1.f);
 }
 
+// `lane` again, but as a value the compiler cannot see through: an LDS read indexed with it inside a loop stays inside the loop.
+// (Weights staged in LDS are loop-invariant; hoisted into registers they would take the registers their staging was meant to free.)
+__device__ __forceinline__ int opaque_lane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// a + b c with the product rounded on its own (never contracted into an fma)
+__device__ __forceinline__ float add_product(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a + b * c;
+}
+
 struct Corners {
   int x0, y0;
   float fx, fy;       // fractional parts (weights of the +1 corners)
@@ -45,6 +58,29 @@ __device__ __forceinline__ Corners corners_of(float vx, float vy, int W, int H) 
 // ---------------------------------------------------------------------------------------------
 // offsets forward: one wave per output point (bg, ty, tx); lane = channel (CPL channels per lane)
 // ---------------------------------------------------------------------------------------------
+// end of a point: o0 / o1 = this lane's part of the 1x1 conv's two outputs -> wave sums -> tanh, grid, normalised position
+__device__ __forceinline__ void offsets_fwd_store(float o0, float o1, int lane, float* __restrict__ vgrid, float* __restrict__ vs,
+                                                  int bg, int j, int ty, int tx, int J, int th, int tw, int PD, float offset_scale) {
+  o0 = wave_sum(o0);
+  if (PD == 2) o1 = wave_sum(o1);
+  if (lane == 0) {
+    if (PD == 2) {
+      const float vg0 = __fadd_rn((float)tx, tanhf(o0) * offset_scale);
+      const float vg1 = __fadd_rn((float)ty, tanhf(o1) * offset_scale);
+      vgrid[((size_t)bg * 2 + 0) * J + j] = vg0;
+      vgrid[((size_t)bg * 2 + 1) * J + j] = vg1;
+      // normalize_grid quirk (DeformableAttention2D.py:100-108): channel 0 / (rows - 1), channel 1 / (cols - 1)
+      vs[((size_t)bg * J + j) * 2 + 0] = normalize_pos(vg0, max(th - 1, 1));
+      vs[((size_t)bg * J + j) * 2 + 1] = normalize_pos(vg1, max(tw - 1, 1));
+    } else {
+      const float vg0 = __fadd_rn((float)tx, tanhf(o0) * offset_scale);
+      vgrid[(size_t)bg * J + j] = vg0;
+      vs[(size_t)bg * J + j] = normalize_pos(vg0, max(tw - 1, 1));
+    }
+  }
+}
+
+// any kernel size, taps in run-time loops (the sizes the path uses have offsets_fwd_taps_kernel below)
 template <int CPL>
 __global__ __launch_bounds__(256) void offsets_fwd_kernel(
     const float* __restrict__ q, const float* __restrict__ w0, const float* __restrict__ b0,
@@ -83,21 +119,84 @@ __global__ __launch_bounds__(256) void offsets_fwd_kernel(
     o0 = fmaf(ge, w2[ch], o0);
     if (PD == 2) o1 = fmaf(ge, w2[dg + ch], o1);
   }
-  o0 = wave_sum(o0);
-  if (PD == 2) o1 = wave_sum(o1);
-  if (lane == 0) {
-    if (PD == 2) {
-      const float vg0 = __fadd_rn((float)tx, tanhf(o0) * offset_scale);
-      const float vg1 = __fadd_rn((float)ty, tanhf(o1) * offset_scale);
-      vgrid[((size_t)bg * 2 + 0) * J + j] = vg0;
-      vgrid[((size_t)bg * 2 + 1) * J + j] = vg1;
-      // normalize_grid quirk (DeformableAttention2D.py:100-108): channel 0 / (rows - 1), channel 1 / (cols - 1)
-      vs[((size_t)bg * J + j) * 2 + 0] = normalize_pos(vg0, max(th - 1, 1));
-      vs[((size_t)bg * J + j) * 2 + 1] = normalize_pos(vg1, max(tw - 1, 1));
-    } else {
-      const float vg0 = __fadd_rn((float)tx, tanhf(o0) * offset_scale);
-      vgrid[(size_t)bg * J + j] = vg0;
-      vs[(size_t)bg * J + j] = normalize_pos(vg0, max(tw - 1, 1));
+  offsets_fwd_store(o0, o1, lane, vgrid, vs, bg, j, ty, tx, J, th, tw, PD, offset_scale);
+}
+
+// The window of sample point `pt` (= (bg, ty, tx), wave-uniform), lane = channel: qv[u][ky * KW + kx] = q at tap (ky, kx), channel
+// lane + 64 u; a tap outside the map (or any tap of a point that does not exist, `live` false) is 0 and its load is NOT issued - the
+// conditions are wave-uniform, so each is a scalar branch around one load.  All loads are issued before the first use.
+template <int CPL, int KH, int KW>
+__device__ __forceinline__ void offsets_load_taps(float (&qv)[CPL][KH * KW], const float* __restrict__ q, bool live, int pt, int lane,
+                                                  int Hh, int Ww, int G, int rh, int rw, int ph, int pw, int tw, int J) {
+  const int dg = 64 * CPL, inner = G * dg;
+  const int bg = pt / J, j = pt - bg * J, b = bg / G, g = bg - b * G;
+  const int ty = j / tw, tx = j - ty * tw;
+#pragma unroll
+  for (int ky = 0; ky < KH; ++ky) {
+    const int iy = ty * rh - ph + ky;
+#pragma unroll
+    for (int kx = 0; kx < KW; ++kx) {
+      const int ix = tx * rw - pw + kx;
+      const bool in = live && iy >= 0 && iy < Hh && ix >= 0 && ix < Ww;
+      const float* src = q + (((size_t)b * Hh + iy) * Ww + ix) * inner + g * dg + lane;
+#pragma unroll
+      for (int u = 0; u < CPL; ++u) qv[u][ky * KW + kx] = in ? src[64 * u] : 0.f;
+    }
+  }
+}
+
+// the instantiated kernel sizes (6 x 6 and 1 x 6, as the backward): the taps of a point are read into registers first - up to
+// KH KW CPL loads in flight per lane where the run-time loops above wait for every tap in turn - and two points are in flight per
+// wave trip; a wave walks pairs of neighbouring points with a grid stride, so the transposed weights are staged once per workgroup
+// for ~10 points per wave.  The fmaf chain then runs from b0[ch] over ALL taps in the (ky, kx) order of the run-time kernel, which
+// SKIPS the taps outside the map: fmaf(w, 0, acc) returns acc itself for every finite w (w * 0 = +-0, and acc + +-0 = acc; only an
+// acc of -0 could turn into +0), so vgrid / vs are bit-identical to that kernel's.
+template <int CPL, int KH, int KW>
+__global__ __launch_bounds__(256) void offsets_fwd_taps_kernel(
+    const float* __restrict__ q, const float* __restrict__ w0, const float* __restrict__ b0,
+    const float* __restrict__ w2, float* __restrict__ vgrid, float* __restrict__ vs, int B, int Hh, int Ww, int G,
+    int rh, int rw, int ph, int pw, int th, int tw, int PD, float offset_scale) {
+  constexpr int KK = KH * KW, dg = 64 * CPL;
+  __shared__ float w0s[KK * dg];              // depthwise weights transposed to [tap][channel]: a wave's read of a tap is one contiguous row
+  for (int i = threadIdx.x; i < dg * KK; i += blockDim.x) {
+    const int ch = i / KK, t = i - ch * KK;
+    w0s[t * dg + ch] = w0[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int J = th * tw, npts = B * G * J;
+  const int nwaves = gridDim.x * (blockDim.x >> 6);
+  float bv[CPL], w2v[CPL][2];
+#pragma unroll
+  for (int u = 0; u < CPL; ++u) {
+    const int ch = lane + 64 * u;
+    bv[u] = b0[ch];
+    w2v[u][0] = w2[ch];
+    w2v[u][1] = (PD == 2) ? w2[dg + ch] : 0.f;
+  }
+  const int wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  for (int p0 = 2 * wave0; p0 < npts; p0 += 2 * nwaves) {
+    float qv[2][CPL][KK];
+    const int wl = opaque_lane(lane);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      offsets_load_taps<CPL, KH, KW>(qv[s], q, p0 + s < npts, min(p0 + s, npts - 1), lane, Hh, Ww, G, rh, rw, ph, pw, tw, J);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int pt = p0 + s;
+      if (pt >= npts) break;
+      float o0 = 0.f, o1 = 0.f;
+#pragma unroll
+      for (int u = 0; u < CPL; ++u) {
+        float acc = bv[u];
+#pragma unroll
+        for (int t = 0; t < KK; ++t) acc = fmaf(w0s[t * dg + wl + 64 * u], qv[s][u][t], acc);
+        const float ge = gelu_erf(acc);
+        o0 = fmaf(ge, w2v[u][0], o0);
+        if (PD == 2) o1 = fmaf(ge, w2v[u][1], o1);
+      }
+      const int bg = pt / J, j = pt - bg * J, ty = j / tw, tx = j - ty * tw;
+      offsets_fwd_store(o0, o1, lane, vgrid, vs, bg, j, ty, tx, J, th, tw, PD, offset_scale);
     }
   }
 }
@@ -106,7 +205,7 @@ __global__ __launch_bounds__(256) void offsets_fwd_kernel(
 // offsets backward: d vgrid (direct) + d vs  ->  dq, dw0, db0, dw2, in three deterministic passes (no global atomics):
 //   1. point pass: each wave walks sampled points with a grid stride, recomputes the forward, stores the gradient
 //      dy[point][channel] of the depthwise conv's output and keeps its weight-gradient partials in registers; the
-//      workgroup's partials are summed in LDS and written to a slab [workgroup][nred]
+//      workgroup's partials are summed in LDS, wave after wave, and written to a slab [workgroup][nred]
 //   2. gather pass: every q element sums dy . w0 over the (at most ceil(k / r)^2 = 4) windows that cover it
 //      (the scatter form needed 2304 float atomics per point: 92 M per step at B = 8, L2-atomic bound)
 //   3. slab reduction in a fixed order
@@ -117,56 +216,90 @@ __global__ __launch_bounds__(256) void offsets_bwd_kernel(
     const float* __restrict__ w2, const float* __restrict__ dvgrid, const float* __restrict__ dvs,
     float* __restrict__ dyb, float* __restrict__ slab, int B, int Hh,
     int Ww, int G, int rh, int rw, int ph, int pw, int th, int tw, int PD, float offset_scale) {
+  constexpr int KK = KH * KW;
+  __shared__ float red[128 * (KK + 3)];
   const int lane = threadIdx.x & 63;
   const int nwaves = gridDim.x * (blockDim.x >> 6);
   const int J = th * tw, npts = B * G * J;
-  const int dg = 64 * CPL, inner = G * dg;
-  float aw0[CPL][KH * KW], ab0[CPL], aw2[CPL][2];
+  const int dg = 64 * CPL;
+  // Everything a lane reads that does not change from point to point stays on chip for the whole walk: b0 / w2 in registers, the
+  // depthwise weights transposed to [tap][channel] in LDS (the space of `red`, which is not needed before the walk ends) - in
+  // registers (where the compiler hoists them to when the loop reads w0 directly) they cost KK CPL registers that the prefetch below
+  // needs.
+  float* wT = red;
+  for (int i = threadIdx.x; i < dg * KK; i += blockDim.x) {
+    const int ch = i / KK, t = i - ch * KK;
+    wT[t * dg + ch] = w0[i];
+  }
+  float bv[CPL], w2v[CPL][2];
+#pragma unroll
+  for (int u = 0; u < CPL; ++u) {
+    const int ch = lane + 64 * u;
+    bv[u] = b0[ch];
+    w2v[u][0] = w2[ch];
+    w2v[u][1] = (PD == 2) ? w2[dg + ch] : 0.f;
+  }
+  __syncthreads();
+  float aw0[CPL][KK], ab0[CPL], aw2[CPL][2];
 #pragma unroll
   for (int u = 0; u < CPL; ++u) {
     ab0[u] = 0.f; aw2[u][0] = 0.f; aw2[u][1] = 0.f;
 #pragma unroll
-    for (int t = 0; t < KH * KW; ++t) aw0[u][t] = 0.f;
+    for (int t = 0; t < KK; ++t) aw0[u][t] = 0.f;
   }
-  for (int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); wid < npts; wid += nwaves) {
-    const int bg = wid / J, j = wid - bg * J, b = bg / G, g = bg - b * G;
-    const int ty = j / tw, tx = j - ty * tw;
+  // the upstream gradients of a point as stored (0 where the tensor is absent): [0 / 1] d vgrid, [2 / 3] d vs
+  auto load_up = [&](float (&up)[4], bool live, int pt) {
+    const int bg = pt / J, j = pt - bg * J;
+    up[0] = up[1] = up[2] = up[3] = 0.f;
+    if (!live) return;
+    if (PD == 2) {
+      if (dvgrid) { up[0] = dvgrid[((size_t)bg * 2 + 0) * J + j]; up[1] = dvgrid[((size_t)bg * 2 + 1) * J + j]; }
+      if (dvs) { up[2] = dvs[((size_t)bg * J + j) * 2 + 0]; up[3] = dvs[((size_t)bg * J + j) * 2 + 1]; }
+    } else {
+      if (dvgrid) up[0] = dvgrid[(size_t)bg * J + j];
+      if (dvs) up[2] = dvs[(size_t)bg * J + j];
+    }
+  };
+  const int wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  // software pipeline over the wave's points: the taps and upstream gradients of the NEXT point are in flight during the arithmetic
+  // of the current one (one memory latency per point instead of one for the taps and more for the gradients behind them)
+  float qn[CPL][KK], upn[4];
+  offsets_load_taps<CPL, KH, KW>(qn, q, wave0 < npts, min(wave0, npts - 1), lane, Hh, Ww, G, rh, rw, ph, pw, tw, J);
+  load_up(upn, wave0 < npts, min(wave0, npts - 1));
+  for (int wid = wave0; wid < npts; wid += nwaves) {
+    const int wl = opaque_lane(lane);
+    float qv[CPL][KK], up[4];            // the window's taps: read once, used by the recompute and by the weight gradient
+#pragma unroll
+    for (int u = 0; u < CPL; ++u)
+#pragma unroll
+      for (int t = 0; t < KK; ++t) qv[u][t] = qn[u][t];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) up[i] = upn[i];
+    const int nxt = wid + nwaves;
+    offsets_load_taps<CPL, KH, KW>(qn, q, nxt < npts, min(nxt, npts - 1), lane, Hh, Ww, G, rh, rw, ph, pw, tw, J);
+    load_up(upn, nxt < npts, min(nxt, npts - 1));
     // recompute the forward
     float y[CPL], ge[CPL];
-    float qv[CPL][KH * KW];                  // the window's taps: read once, used by the recompute and by the weight gradient
     float o0 = 0.f, o1 = 0.f;
 #pragma unroll
     for (int u = 0; u < CPL; ++u) {
-      const int ch = lane + 64 * u;
-      float acc = b0[ch];
+      float acc = bv[u];
 #pragma unroll
-      for (int ky = 0; ky < KH; ++ky) {
-        const int iy = ty * rh - ph + ky;
-#pragma unroll
-        for (int kx = 0; kx < KW; ++kx) {
-          const int ix = tx * rw - pw + kx;
-          const bool in = iy >= 0 && iy < Hh && ix >= 0 && ix < Ww;
-          qv[u][ky * KW + kx] = in ? q[(((size_t)b * Hh + iy) * Ww + ix) * inner + g * dg + ch] : 0.f;
-          acc = fmaf(w0[(ch * KH + ky) * KW + kx], qv[u][ky * KW + kx], acc);
-        }
-      }
+      for (int t = 0; t < KK; ++t) acc = fmaf(wT[t * dg + wl + 64 * u], qv[u][t], acc);
       y[u] = acc;
       ge[u] = gelu_erf(acc);
-      o0 = fmaf(ge[u], w2[ch], o0);
-      if (PD == 2) o1 = fmaf(ge[u], w2[dg + ch], o1);
+      o0 = fmaf(ge[u], w2v[u][0], o0);
+      if (PD == 2) o1 = fmaf(ge[u], w2v[u][1], o1);
     }
     o0 = wave_sum(o0);
     if (PD == 2) o1 = wave_sum(o1);
-    // upstream gradient of vgrid = direct part + 2 / max(t - 1, 1) * d vs
+    // upstream gradient of vgrid = direct part + 2 / max(t - 1, 1) * d vs (product and sum rounded separately)
     float g0, g1 = 0.f;
     if (PD == 2) {
-      g0 = (dvgrid ? dvgrid[((size_t)bg * 2 + 0) * J + j] : 0.f) +
-           (dvs ? dvs[((size_t)bg * J + j) * 2 + 0] * (2.f / (float)max(th - 1, 1)) : 0.f);
-      g1 = (dvgrid ? dvgrid[((size_t)bg * 2 + 1) * J + j] : 0.f) +
-           (dvs ? dvs[((size_t)bg * J + j) * 2 + 1] * (2.f / (float)max(tw - 1, 1)) : 0.f);
+      g0 = add_product(up[0], up[2], 2.f / (float)max(th - 1, 1));
+      g1 = add_product(up[1], up[3], 2.f / (float)max(tw - 1, 1));
     } else {
-      g0 = (dvgrid ? dvgrid[(size_t)bg * J + j] : 0.f) +
-           (dvs ? dvs[(size_t)bg * J + j] * (2.f / (float)max(tw - 1, 1)) : 0.f);
+      g0 = add_product(up[0], up[2], 2.f / (float)max(tw - 1, 1));
     }
     const float t0 = tanhf(o0), t1 = tanhf(o1);
     const float ds0 = g0 * offset_scale * (1.f - t0 * t0);
@@ -175,32 +308,37 @@ __global__ __launch_bounds__(256) void offsets_bwd_kernel(
     for (int u = 0; u < CPL; ++u) {
       const int ch = lane + 64 * u;
       aw2[u][0] = fmaf(ds0, ge[u], aw2[u][0]);
-      float dge = ds0 * w2[ch];
+      float dge = ds0 * w2v[u][0];
       if (PD == 2) {
         aw2[u][1] = fmaf(ds1, ge[u], aw2[u][1]);
-        dge = fmaf(ds1, w2[dg + ch], dge);
+        dge = fmaf(ds1, w2v[u][1], dge);
       }
       const float dy = dge * gelu_erf_grad(y[u]);
       dyb[(size_t)wid * dg + ch] = dy;
       ab0[u] += dy;
 #pragma unroll
-      for (int t = 0; t < KH * KW; ++t) aw0[u][t] = fmaf(dy, qv[u][t], aw0[u][t]);   // taps outside the map are 0
+      for (int t = 0; t < KK; ++t) aw0[u][t] = fmaf(dy, qv[u][t], aw0[u][t]);   // taps outside the map are 0
     }
   }
   // weight-gradient partials: sum the workgroup's waves in LDS, then one contiguous slab row per workgroup
-  __shared__ float red[128 * (KH * KW + 3)];
-  constexpr int KK = KH * KW;
   const int nred = dg * (KK + 1 + 2);
+  __syncthreads();                         // every wave is done with the transposed weights: their space becomes `red`
   for (int i = threadIdx.x; i < nred; i += blockDim.x) red[i] = 0.f;
-  __syncthreads();
+  // the waves add their partials one after the other, wave 0 first: a fixed order (LDS float atomics arrive in the order the waves
+  // happen to finish their walks, and the sums differed in the last bits from run to run)
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+    __syncthreads();
+    if ((int)(threadIdx.x >> 6) == w) {
 #pragma unroll
-  for (int u = 0; u < CPL; ++u) {
-    const int ch = lane + 64 * u;
+      for (int u = 0; u < CPL; ++u) {
+        const int ch = lane + 64 * u;
 #pragma unroll
-    for (int t = 0; t < KK; ++t) atomicAdd(&red[ch * KK + t], aw0[u][t]);
-    atomicAdd(&red[dg * KK + ch], ab0[u]);
-    atomicAdd(&red[dg * (KK + 1) + ch], aw2[u][0]);
-    if (PD == 2) atomicAdd(&red[dg * (KK + 2) + ch], aw2[u][1]);
+        for (int t = 0; t < KK; ++t) red[ch * KK + t] += aw0[u][t];
+        red[dg * KK + ch] += ab0[u];
+        red[dg * (KK + 1) + ch] += aw2[u][0];
+        if (PD == 2) red[dg * (KK + 2) + ch] += aw2[u][1];
+      }
+    }
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nred; i += blockDim.x) slab[(size_t)blockIdx.x * nred + i] = red[i];
@@ -385,6 +523,20 @@ int smml_offsets_fwd_f32(const float* q, const float* w0, const float* b0, const
   const int npts = B * G * th * tw;
   dim3 grid((npts + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
+  if (ks == 6) {
+    // two points per wave trip, four waves per workgroup; at most 1024 workgroups (all resident), the rest by grid stride
+    dim3 tgrid(min((npts + 7) / 8, 1024));
+#define SMML_OFFSETS_FWD(CPL, KH)                                                                                              \
+    hipLaunchKernelGGL((offsets_fwd_taps_kernel<CPL, KH, 6>), tgrid, block, 0, st, q, w0, b0, w2, vgrid, vs, B, Hh, Ww, G, rh, r, \
+                       ph, pw, th, tw, posdim, offset_scale)
+    if (posdim == 2 && dg == 64) SMML_OFFSETS_FWD(1, 6);
+    else if (posdim == 2) SMML_OFFSETS_FWD(2, 6);
+    else if (dg == 64) SMML_OFFSETS_FWD(1, 1);
+    else SMML_OFFSETS_FWD(2, 1);
+#undef SMML_OFFSETS_FWD
+    SMML_LAUNCH_CHECK("smml_offsets_fwd_f32");
+    return SMML_OK;
+  }
   const size_t lds = (size_t)dg * kh * ks * sizeof(float);
   if (dg == 64)
     hipLaunchKernelGGL(offsets_fwd_kernel<1>, grid, block, lds, st, q, w0, b0, w2, vgrid, vs, B, Hh, Ww, G, kh, ks, rh,

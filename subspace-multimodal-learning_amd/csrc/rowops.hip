@@ -2,8 +2,10 @@
 //   LayerNorm forward / backward          (models/DeformCrossTransMIL.py:44,71,75,90,144; mil.py:175,187)
 //   column sums / means over tokens       (Pooler mean, DeformCrossTransMIL.py:193; bias gradients)
 //   ReLU backward                         (_fc1, DeformCrossTransMIL.py:83)
-// One wave per row, 16-byte accesses when the row length allows it (C % 256 == 0 uses float4 per lane,
-// otherwise scalar with a 64-lane stride); partial column sums leave a workgroup through float atomics.
+// LayerNorm: the generic kernels put one wave on one row (lane l owns columns l, l + 64, ...; C <= 1024); at C = 128 - the path's token
+// width - that is one 512-byte row in flight per wave and latency-bound, so both directions have a 128-column kernel: a half-wave per
+// row, one float4 per lane, several rows of loads in flight per wave, grid-stride loop.  Partial column sums leave a workgroup
+// through float atomics.
 #include <algorithm>
 #include "smml_common.h"
 
@@ -51,6 +53,61 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
   }
   if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+}
+
+// sum over the 128 columns of a row held by a half-wave (lane hl: columns 4 hl .. 4 hl + 3), IN THE ORDER OF wave_sum() OVER THE GENERIC
+// KERNEL'S LAYOUT, so that the 128-column kernel returns the generic kernel's bits: there lane l first adds columns l and l + 64 (the
+// "leaf" t), then neighbouring lanes are added pairwise at distances 1, 2, 4, 8 inside each row of 16 lanes, then the four rows from
+// left to right.  t0..t3: the leaves of columns 4 (hl & 15) + 0..3 - lanes hl and hl ^ 16 hold the same four
+__device__ __forceinline__ float row128_sum(float t0, float t1, float t2, float t3) {
+  float v = (t0 + t1) + (t2 + t3);
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);                                        // lanes 4 k .. 4 k + 3: columns 16 k .. 16 k + 15 (and + 64)
+  const float r0 = __shfl(v, 0, 32), r1 = __shfl(v, 4, 32), r2 = __shfl(v, 8, 32), r3 = __shfl(v, 12, 32);
+  return ((r0 + r1) + r2) + r3;
+}
+
+// C = 128 (the path's token width), the forward sibling of layernorm_bwd128_kernel: a half-wave per row, one float4 per lane,
+// LN128_RPT rows per half-wave and trip - eight rows of loads in flight per wave instead of one.  Two-pass (mean, then the centred sum
+// of squares) with every sum and product in the generic kernel's order (row128_sum; leaf of the squares = fma(d_hi, d_hi, d_lo d_lo);
+// y = fma(d rstd, gamma, beta)): y, mean and rstd are bit-identical to layernorm_fwd_kernel's.
+constexpr int LN128_RPT = 4;
+__global__ __launch_bounds__(256) void layernorm_fwd128_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float* __restrict__ y,
+                                                               float* __restrict__ mean, float* __restrict__ rstd, long long R,
+                                                               float eps) {
+  constexpr int C = 128, U = LN128_RPT;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
+  const bool low = hl < 16;                                     // this lane's columns are the c (not the c + 64) of their leaves
+  const float4 gm = *reinterpret_cast<const float4*>(gamma + 4 * hl), bt = *reinterpret_cast<const float4*>(beta + 4 * hl);
+  const long long stride = (long long)gridDim.x * (8 * U);     // rows per trip of the whole grid: 4 waves x 2 halves x U
+  for (long long base = ((long long)blockIdx.x * 4 + wave) * (2 * U); base < R; base += stride) {
+    float4 xv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long row = base + 2 * u + half;
+      xv[u] = *reinterpret_cast<const float4*>(x + (row < R ? row : R - 1) * C + 4 * hl);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long row = base + 2 * u + half;
+      const float4 own = xv[u];
+      const float4 oth = make_float4(__shfl_xor(own.x, 16), __shfl_xor(own.y, 16), __shfl_xor(own.z, 16), __shfl_xor(own.w, 16));
+      const float4 lo = low ? own : oth, hi = low ? oth : own;
+      const float mu = row128_sum((0.f + lo.x) + hi.x, (0.f + lo.y) + hi.y, (0.f + lo.z) + hi.z, (0.f + lo.w) + hi.w) / (float)C;
+      const float4 dl = make_float4(lo.x - mu, lo.y - mu, lo.z - mu, lo.w - mu);
+      const float4 dh = make_float4(hi.x - mu, hi.y - mu, hi.z - mu, hi.w - mu);
+      const float ss = row128_sum(fmaf(dh.x, dh.x, dl.x * dl.x), fmaf(dh.y, dh.y, dl.y * dl.y), fmaf(dh.z, dh.z, dl.z * dl.z),
+                                  fmaf(dh.w, dh.w, dl.w * dl.w));
+      const float rs = rsqrtf(ss / (float)C + eps);
+      if (row < R) {
+        const float4 d = low ? dl : dh;
+        *reinterpret_cast<float4*>(y + row * C + 4 * hl) = make_float4(fmaf(d.x * rs, gm.x, bt.x), fmaf(d.y * rs, gm.y, bt.y),
+                                                                       fmaf(d.z * rs, gm.z, bt.z), fmaf(d.w * rs, gm.w, bt.w));
+        if (hl == 0) { mean[row] = mu; rstd[row] = rs; }
+      }
+    }
+  }
 }
 
 // dx (+)= rstd * (g dy - mean(g dy) - xhat * mean(g dy xhat)); dgamma += sum dy xhat; dbeta += sum dy
@@ -366,6 +423,13 @@ int smml_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta
                            long long R, int C, float eps, void* stream) {
   SMML_REQUIRE(x && gamma && beta && y && mean && rstd, "smml_layernorm_fwd_f32: null pointer");
   SMML_REQUIRE(R > 0 && C > 0 && C <= 64 * MAXV, "smml_layernorm_fwd_f32: need 0 < C <= %d (got %d)", 64 * MAXV, C);
+  const bool aligned = ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(gamma) |
+                         reinterpret_cast<size_t>(beta)) & 15) == 0;
+  if (C == 128 && aligned) {
+    const long long nb = (R + 8 * LN128_RPT - 1) / (8 * LN128_RPT);
+    hipLaunchKernelGGL(layernorm_fwd128_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, (hipStream_t)stream, x, gamma,
+                       beta, y, mean, rstd, R, eps);
+  } else
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma,
                      beta, y, mean, rstd, R, C, eps);
   SMML_LAUNCH_CHECK("smml_layernorm_fwd_f32");
