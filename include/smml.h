@@ -52,6 +52,20 @@ int smml_gemm_f32(const float* A, const float* B, float* C, const float* bias, c
                   long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
                   long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
                   int splitk, int accumulate, float alpha, float beta, void* stream);
+/* Deterministic form of the split-K / folded-batch products (functional.deterministic): same arguments plus a workspace.  The product
+ * kernels store alpha A B of every (batch item, split-K slice) z = (b0 nb1 + b1) splitk + ks densely at workspace[z][m][n]; a second kernel
+ * owns one element of C per thread and adds, in ascending z, the splitk slices of its batch item and - for a batch dimension folded onto
+ * one C (sc0 / sc1 = 0) - every item of that dimension.  C is overwritten with the sum (accumulate != 0: the sum is added onto what C
+ * holds); no float atomics.  bias, residual and act must be NULL / 0.
+ * workspace: smml_gemm_f32_det_workspace_bytes = nb0 nb1 splitk M N 4 bytes, 16-byte aligned. */
+size_t smml_gemm_f32_det_workspace_bytes(int M, int N, int nb0, int nb1, int splitk);
+int smml_gemm_f32_det(const float* A, const float* B, float* C, const float* bias, const float* residual,
+                      int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
+                      long long ldc, long long ldr, int nb0, int nb1, long long sa0, long long sa1,
+                      long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
+                      long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
+                      int splitk, int accumulate, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                      void* stream);
 /* test hook: 1 routes every product through the generic (any stride / any K) kernel instead of the tiled
  * fast path (K % 16 == 0, 16-byte aligned operands with a unit stride on k or on the row index). */
 void smml_gemm_force_generic(int on);
@@ -98,10 +112,25 @@ int smml_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta
 int smml_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, const float* mean,
                            const float* rstd, float* dx, float* dgamma, float* dbeta, long long R, int C,
                            long long rows_per_dy, float dy_scale, int accumulate_dx, void* stream);
+/* Deterministic form: the workgroups write their dgamma / dbeta rows to workspace[workgroup][2][C] and a second kernel adds them in a
+ * fixed order ONTO dgamma / dbeta (the accumulate-into contract above); dx is smml_layernorm_bwd_f32's, bit for bit.
+ * workspace: W 2 C 4 bytes with W = min(ceil(R / 16), 768) at C = 128 and min(ceil(R / 4), 1024) otherwise, 16-byte aligned. */
+size_t smml_layernorm_bwd_det_workspace_bytes(long long R, int C);
+int smml_layernorm_bwd_det_f32(const float* x, const float* dy, const float* gamma, const float* mean,
+                               const float* rstd, float* dx, float* dgamma, float* dbeta, long long R, int C,
+                               long long rows_per_dy, float dy_scale, int accumulate_dx, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* out[b, c] += scale * sum_r x[b, r, c] for x [nb, R, C]; out accumulated into.
  * Pooler mean (DeformCrossTransMIL.py:193) and bias gradients. */
 int smml_colsum_f32(const float* x, float* out, int nb, long long R, int C, float scale, void* stream);
+/* Deterministic form: out[b, c] = scale * sum_r x[b, r, c], OVERWRITTEN.  The rows are cut into chunks that depend on (R, C) alone; the
+ * chunk sums (scaled) go to workspace[chunk][b][C] and a second kernel adds the chunks in a fixed order.
+ * workspace: ceil(R / rpc) nb C 4 bytes, 16-byte aligned, with rows per chunk rpc = 256, or - where C % 4 == 0, C <= 1024 and C / 4 divides
+ * 256 - max(64 rl, ceil(R / 2048)) rounded up to a multiple of rl = 256 / (C / 4). */
+size_t smml_colsum_det_workspace_bytes(int nb, long long R, int C);
+int smml_colsum_det_f32(const float* x, float* out, int nb, long long R, int C, float scale, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* OrthogonalLoss (models/cmta_utils.py:1212-1228) on rows P, P_hat, G, G_hat [B, D]: loss [B] (nullable) and, when
  * dloss [B] is given, dP / dPh / dG / dGh [B, D]; one wave per sample, wavefront reductions. */
@@ -148,6 +177,15 @@ int smml_bilinear_sample_fwd_f32(const float* x, const float* vs, float* kv, int
 /* dx accumulated into (float atomics); dvs accumulated into (+=). */
 int smml_bilinear_sample_bwd_f32(const float* x, const float* vs, const float* dkv, float* dx, float* dvs,
                                  int B, int Hh, int Ww, int G, int cg, int J, int posdim, void* stream);
+/* Deterministic form: dx is OVERWRITTEN by a gather.  Per (bag, group) the 4 J corner contributions are sorted in LDS by the unique key
+ * pixel 2^14 + (4 j + corner) (corners outside the map form a run nobody reads); every (pixel, channel) then adds its pixel's run in sorted
+ * order, pixels nobody samples get 0 - no float atomics.  dvs is accumulated into (+=) exactly as above.
+ * cg 16 or 32, J <= 4096, Hh Ww <= 262142 (an error otherwise).
+ * workspace: B G (4 J + Hh Ww + 1) 4 bytes (the sorted keys and the start of every pixel's run), 16-byte aligned. */
+size_t smml_bilinear_sample_bwd_det_workspace_bytes(int B, int Hh, int Ww, int G, int J);
+int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const float* dkv, float* dx, float* dvs,
+                                     void* workspace, size_t workspace_bytes, int B, int Hh, int Ww, int G, int cg,
+                                     int J, int posdim, void* stream);
 /* integer path only (bit-exact contract): corner indices cx, cy [n, 4] and in-bounds masks cm [n, 4]
  * in the order (x0,y0) (x1,y0) (x0,y1) (x1,y1) for n sample points vs [n, posdim]. */
 int smml_bilinear_corners_f32(const float* vs, int* cx, int* cy, unsigned char* cm, int n, int Hh, int Ww,

@@ -9,6 +9,7 @@ Python identifier).  No CPU fallback: the kernels need a gfx950 device."""
 from . import synth  # noqa: F401  (no GPU dependency)
 from ._capi import LIB_PATH, SIGNATURES, lib  # noqa: F401
 from . import functional  # noqa: F401
+from .functional import deterministic, is_deterministic, set_deterministic  # noqa: F401
 from .deform_attention import CPB, DeformCrossAttention1D, DeformCrossAttention2D, Scale  # noqa: F401
 from .deform_cross_trans_mil import DeformCrossTransLayer, DeformCrossTransMIL, FusionNet, Pooler  # noqa: F401
 from .nystrom_attention import NystromAttention, PPEG, TransLayer, TransMIL, moore_penrose_iter_pinv  # noqa: F401
@@ -25,4 +26,5 @@ __all__ = [
     "CPB", "Scale", "DeformCrossAttention1D", "DeformCrossAttention2D", "FusionNet", "DeformCrossTransLayer",
     "DeformCrossTransMIL", "Pooler", "NystromAttention", "TransLayer", "PPEG", "TransMIL", "moore_penrose_iter_pinv", "MultiheadAttention", "CMTA", "Transformer_P", "Transformer_G", "SNN_Block", "BilinearFusion", "define_bifusion", "MaxNet", "DeformPathomicNet", "define_net", "BatchLoss", "GatherLayer",
     "OrthogonalLoss", "BagDataParallel", "gradient_modulate", "gradient_modulate_survival", "PinnedBagStager", "BagStore", "BagStoreWriter", "BagStoreDataset", "fixdim_gather", "fixdim_indices", "functional", "synth", "lib",
+    "deterministic", "set_deterministic", "is_deterministic",
 ]

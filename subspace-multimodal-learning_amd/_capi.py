@@ -35,6 +35,9 @@ SIGNATURES = {
     "smml_device_check": (_i, [_i]),
     "smml_gemm_f32": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _ll, _ll, _ll, _ll,
                            _ll, _ll, _ll, _ll, _i, _i, _ll, _i, _i, _i, _fl, _fl, _f]),
+    "smml_gemm_f32_det_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "smml_gemm_f32_det": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _ll, _ll, _ll, _ll,
+                               _ll, _ll, _ll, _ll, _i, _i, _ll, _i, _i, _i, _fl, _fl, _f, _sz, _f]),
     "smml_gemm_force_generic": (None, [_i]),
     "smml_gemm_set_mode": (None, [_i]),
     "smml_gemm_get_mode": (_i, []),
@@ -53,7 +56,11 @@ SIGNATURES = {
     "smml_attn16_bwd_f32": (_i, [_f] * 10 + [_f, _sz, _i, _i, _i, _i, _fl, _i, _i, _f]),
     "smml_layernorm_fwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _ll, _i, _fl, _f]),
     "smml_layernorm_bwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _ll, _i, _ll, _fl, _i, _f]),
+    "smml_layernorm_bwd_det_workspace_bytes": (_sz, [_ll, _i]),
+    "smml_layernorm_bwd_det_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _ll, _i, _ll, _fl, _i, _f, _sz, _f]),
     "smml_colsum_f32": (_i, [_f, _f, _i, _ll, _i, _fl, _f]),
+    "smml_colsum_det_workspace_bytes": (_sz, [_i, _ll, _i]),
+    "smml_colsum_det_f32": (_i, [_f, _f, _i, _ll, _i, _fl, _f, _sz, _f]),
     "smml_orth_loss_f32": (_i, [_f] * 10 + [_i, _i, _fl, _f]),
     "smml_batchloss_tail_f32": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _fl, _f]),
     "smml_relu_bwd_f32": (_i, [_f, _f, _f, _ll, _f]),
@@ -63,6 +70,8 @@ SIGNATURES = {
     "smml_offsets_bwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _i, _f]),
     "smml_bilinear_sample_fwd_f32": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
     "smml_bilinear_sample_bwd_f32": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "smml_bilinear_sample_bwd_det_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "smml_bilinear_sample_bwd_det_f32": (_i, [_f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _f]),
     "smml_bilinear_corners_f32": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "smml_deform_attn_nst": (_i, [_i]),
     "smml_deform_attn_fwd_f32": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),

@@ -28,6 +28,7 @@ struct GemmArgs {
   int act, splitk; float alpha, beta;
   int atomic;    // accumulate into C with float atomics (split-K, or batch dims folded onto one C)
   int swap_xy;   // column tiles on grid.x (wide outputs: > 65535 column tiles)
+  long long scs; // C stride of a split-K slice: 0 (the slices share one C) or, in the partial-output mode of smml_gemm_f32_det, M * N
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   const int b0 = zb / g.nb1, b1 = zb - b0 * g.nb1;
   const float* A = g.A + b0 * g.sa0 + b1 * g.sa1;
   const float* B = g.B + b0 * g.sb0 + b1 * g.sb1;
-  float* C = g.C + b0 * g.sc0 + b1 * g.sc1;
+  float* C = g.C + b0 * g.sc0 + b1 * g.sc1 + ks * g.scs;
   const int m0 = (g.swap_xy ? blockIdx.y : blockIdx.x) * BM, n0 = (g.swap_xy ? blockIdx.x : blockIdx.y) * BN;
   // K range of this split, in whole BK tiles
   const int ktiles = (g.K + BK - 1) / BK;
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_fast_kernel(GemmArgs g) {
   const int b0 = zb / g.nb1, b1 = zb - b0 * g.nb1;
   const float* A = g.A + b0 * g.sa0 + b1 * g.sa1;
   const float* B = g.B + b0 * g.sb0 + b1 * g.sb1;
-  float* C = g.C + b0 * g.sc0 + b1 * g.sc1;
+  float* C = g.C + b0 * g.sc0 + b1 * g.sc1 + ks * g.scs;
   const int m0 = (g.swap_xy ? blockIdx.y : blockIdx.x) * FBM, n0 = (g.swap_xy ? blockIdx.x : blockIdx.y) * BN_;
   const int ktiles = (g.K + FBK - 1) / FBK;         // a K tail is zero-filled at load time
   const int tps = (ktiles + g.splitk - 1) / g.splitk;
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(GemmArgs g) {
   const int b0 = zb / g.nb1, b1 = zb - b0 * g.nb1;
   const float* A = g.A + b0 * g.sa0 + b1 * g.sa1;
   const float* B = g.B + b0 * g.sb0 + b1 * g.sb1;
-  float* C = g.C + b0 * g.sc0 + b1 * g.sc1;
+  float* C = g.C + b0 * g.sc0 + b1 * g.sc1 + ks * g.scs;
   const int m0 = (g.swap_xy ? blockIdx.y : blockIdx.x) * FBM, n0 = (g.swap_xy ? blockIdx.x : blockIdx.y) * BN_;
   const int ktiles = (g.K + FBK - 1) / FBK;                    // a K tail is zero-filled at load time
   const int tps = (ktiles + g.splitk - 1) / g.splitk;
@@ -558,6 +559,33 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(GemmArgs g) {
     }
 }
 
+// Deterministic split-K / folded-batch sum (smml_gemm_f32_det): the product kernels above ran in their plain-store mode with workgroup
+// blockIdx.z = z writing its tile of alpha A B densely to part[z][m][n]; here one thread owns one element of C and adds, in ascending z,
+// every slice that addresses it - the splitk slices of its batch item and, for a batch dimension folded onto one C (stride 0), every item
+// of that dimension.  No atomics: the sum is a fixed function of the operands.
+__global__ __launch_bounds__(256) void gemm_det_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N,
+                                                              long long ldc, int nb0, int nb1, long long sc0, long long sc1, int splitk,
+                                                              int fold0, int fold1, int accumulate) {
+  const int e1 = fold1 ? 1 : nb1;
+  const long long mn = (long long)M * N;
+  const long long total = (long long)(fold0 ? 1 : nb0) * e1 * mn;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const long long o = idx / mn, r = idx - o * mn;
+  const int o0 = (int)(o / e1), o1 = (int)(o - (long long)o0 * e1);
+  const int b0a = fold0 ? 0 : o0, b0b = fold0 ? nb0 : o0 + 1;
+  const int b1a = fold1 ? 0 : o1, b1b = fold1 ? nb1 : o1 + 1;
+  float s = 0.f;
+  for (int b0 = b0a; b0 < b0b; ++b0)
+    for (int b1 = b1a; b1 < b1b; ++b1) {
+      const float* p = part + ((long long)b0 * nb1 + b1) * splitk * mn + r;
+      for (int ks = 0; ks < splitk; ++ks) s += p[ks * mn];
+    }
+  const long long m = r / N, n = r - m * N;
+  float* c = C + o0 * sc0 + o1 * sc1 + m * ldc + n;
+  *c = accumulate ? *c + s : s;
+}
+
 }  // namespace
 
 static std::atomic<int> g_force_generic{0};   // test hook: route everything through the generic kernel
@@ -570,20 +598,21 @@ extern "C" int smml_gemm_get_mode(void) { return g_mode; }
 static std::atomic<int> g_small_tile{0};      // 0: automatic, 1: never use the 64-row tile, 2: use it wherever it applies (measurement hooks)
 extern "C" void smml_gemm_set_small_tile(int v) { g_small_tile = v; }
 
-extern "C" int smml_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
-                             int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
-                             long long ldc, long long ldr, int nb0, int nb1, long long sa0, long long sa1,
-                             long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
-                             long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
-                             int splitk, int accumulate, float alpha, float beta, void* stream) {
-  SMML_REQUIRE(A && B && C, "smml_gemm_f32: null operand");
-  SMML_REQUIRE(M > 0 && N > 0 && K > 0 && nb0 > 0 && nb1 > 0, "smml_gemm_f32: non-positive size (M=%d N=%d K=%d)", M, N, K);
-  SMML_REQUIRE(splitk >= 1, "smml_gemm_f32: splitk must be >= 1");
-  const int atomic = (splitk > 1 || accumulate) ? 1 : 0;
-  SMML_REQUIRE(!(atomic && (act != 0 || residual)), "smml_gemm_f32: split-K / accumulate excludes activation/residual");
-  SMML_REQUIRE(bias_mode >= 0 && bias_mode <= 2, "smml_gemm_f32: bad bias_mode %d", bias_mode);
-  SMML_REQUIRE(bias_mode != 2 || rows_per_bias > 0, "smml_gemm_f32: rows_per_bias must be positive");
-  SMML_REQUIRE(act >= 0 && act <= 2, "smml_gemm_f32: bad activation %d", act);
+// the launch both entry points share: picks the kernel for the operands' layout and runs it.  atomic: the epilogue adds into C with float
+// atomics; scs: C stride between the split-K slices of one batch item (the partial-output mode; 0 otherwise)
+static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C, const float* bias, const float* residual,
+                        int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
+                        long long ldc, long long ldr, int nb0, int nb1, long long sa0, long long sa1,
+                        long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
+                        long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
+                        int splitk, int atomic, long long scs, float alpha, float beta, void* stream) {
+  SMML_REQUIRE(A && B && C, "%s: null operand", fn);
+  SMML_REQUIRE(M > 0 && N > 0 && K > 0 && nb0 > 0 && nb1 > 0, "%s: non-positive size (M=%d N=%d K=%d)", fn, M, N, K);
+  SMML_REQUIRE(splitk >= 1, "%s: splitk must be >= 1", fn);
+  SMML_REQUIRE(!((atomic || scs) && (act != 0 || residual)), "%s: split-K / accumulate excludes activation/residual", fn);
+  SMML_REQUIRE(bias_mode >= 0 && bias_mode <= 2, "%s: bad bias_mode %d", fn, bias_mode);
+  SMML_REQUIRE(bias_mode != 2 || rows_per_bias > 0, "%s: rows_per_bias must be positive", fn);
+  SMML_REQUIRE(act >= 0 && act <= 2, "%s: bad activation %d", fn, act);
   const long long gz = (long long)nb0 * nb1 * splitk;
   const long long gy = (N + BN - 1) / BN, gx = (M + BM - 1) / BM;
   const int swap_xy = gy > 65535;
@@ -591,7 +620,7 @@ extern "C" int smml_gemm_f32(const float* A, const float* B, float* C, const flo
                "smml_gemm_f32: grid too large (batch*splitk=%lld, row tiles=%lld, col tiles=%lld)", gz, gx, gy);
   GemmArgs g{A, B, C, bias_mode ? bias : nullptr, residual, M, N, K, sam, sak, sbk, sbn, ldc, ldr, nb0, nb1,
              sa0, sa1, sb0, sb1, sc0, sc1, sbias0, sbias1, bias_mode, rows_per_bias > 0 ? rows_per_bias : 1,
-             bias_ld, act, splitk, alpha, beta, atomic, swap_xy};
+             bias_ld, act, splitk, alpha, beta, atomic, swap_xy, scs};
   SMML_REQUIRE(!bias_mode || bias, "smml_gemm_f32: bias_mode set but bias is null");
   // fast path: aligned operands with a unit stride on k (then K a multiple of 4: float4 loads along k) or on the row
   // index (any K); the K tail of the last 16-wide tile is zero-filled
@@ -655,5 +684,51 @@ extern "C" int smml_gemm_f32(const float* A, const float* B, float* C, const flo
   dim3 grid((unsigned)(swap_xy ? gy : gx), (unsigned)(swap_xy ? gx : gy), (unsigned)gz);
   hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
   SMML_LAUNCH_CHECK("smml_gemm_f32");
+  return SMML_OK;
+}
+
+extern "C" int smml_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
+                             int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
+                             long long ldc, long long ldr, int nb0, int nb1, long long sa0, long long sa1,
+                             long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
+                             long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
+                             int splitk, int accumulate, float alpha, float beta, void* stream) {
+  const int atomic = (splitk > 1 || accumulate) ? 1 : 0;
+  return gemm_f32_run("smml_gemm_f32", A, B, C, bias, residual, M, N, K, sam, sak, sbk, sbn, ldc, ldr, nb0, nb1, sa0, sa1, sb0, sb1,
+                      sc0, sc1, sbias0, sbias1, bias_mode, rows_per_bias, bias_ld, act, splitk, atomic, 0, alpha, beta, stream);
+}
+
+// partial slab of smml_gemm_f32_det: one dense M x N tile set per (batch item, split-K slice)
+extern "C" size_t smml_gemm_f32_det_workspace_bytes(int M, int N, int nb0, int nb1, int splitk) {
+  if (M <= 0 || N <= 0 || nb0 <= 0 || nb1 <= 0 || splitk <= 0) return 0;
+  return (size_t)nb0 * (size_t)nb1 * (size_t)splitk * (size_t)M * (size_t)N * sizeof(float);
+}
+
+// smml_gemm_f32 for products whose slices (split-K) or batch items (a batch stride of 0 on C) add up in one C, without atomics: the product
+// kernels store alpha A B per (batch item, slice) into the workspace, gemm_det_reduce_kernel adds them in a fixed order and writes C
+// (accumulate: adds the sum onto what C holds).  No bias, activation or residual.
+extern "C" int smml_gemm_f32_det(const float* A, const float* B, float* C, const float* bias, const float* residual,
+                                 int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
+                                 long long ldc, long long ldr, int nb0, int nb1, long long sa0, long long sa1,
+                                 long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
+                                 long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act,
+                                 int splitk, int accumulate, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  SMML_REQUIRE(A && B && C && workspace, "smml_gemm_f32_det: null operand or workspace");
+  SMML_REQUIRE(M > 0 && N > 0 && K > 0 && nb0 > 0 && nb1 > 0 && splitk >= 1, "smml_gemm_f32_det: non-positive size (M=%d N=%d K=%d)", M, N, K);
+  SMML_REQUIRE(!bias && !residual && bias_mode == 0 && act == 0, "smml_gemm_f32_det: the reduced product takes no bias, activation or residual");
+  SMML_REQUIRE((long long)nb0 * nb1 * splitk <= 65535, "smml_gemm_f32_det: batch * splitk = %lld exceeds 65535", (long long)nb0 * nb1 * splitk);
+  SMML_REQUIRE(workspace_bytes >= smml_gemm_f32_det_workspace_bytes(M, N, nb0, nb1, splitk), "smml_gemm_f32_det: workspace too small");
+  const long long mn = (long long)M * N;
+  float* part = (float*)workspace;
+  int rc = gemm_f32_run("smml_gemm_f32_det", A, B, part, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, N, 0, nb0, nb1, sa0, sa1, sb0, sb1,
+                        (long long)nb1 * splitk * mn, (long long)splitk * mn, 0, 0, 0, 1, 0, 0, splitk, 0, mn, alpha, 1.f, stream);
+  if (rc) return rc;
+  const int fold0 = (nb0 > 1 && sc0 == 0), fold1 = (nb1 > 1 && sc1 == 0);
+  const long long total = (long long)(fold0 ? 1 : nb0) * (fold1 ? 1 : nb1) * mn;
+  SMML_REQUIRE((total + 255) / 256 <= 2147483647LL, "smml_gemm_f32_det: output too large");
+  hipLaunchKernelGGL(gemm_det_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, C, M, N, ldc,
+                     nb0, nb1, sc0, sc1, splitk, fold0, fold1, accumulate ? 1 : 0);
+  SMML_LAUNCH_CHECK("smml_gemm_f32_det/reduce");
   return SMML_OK;
 }

@@ -431,7 +431,8 @@ __global__ void sample_fwd_kernel(const float* __restrict__ x, const float* __re
 }
 
 // backward: dx (atomic scatter-add into a zeroed / accumulating buffer), dvs += (unique owner per point)
-template <int CG>
+// SCATTER false (the deterministic entry point): dvs only, with the same arithmetic - dx is gathered by sample_bwd_gather_kernel
+template <int CG, bool SCATTER = true>
 __global__ void sample_bwd_kernel(const float* __restrict__ x, const float* __restrict__ vs,
                                   const float* __restrict__ dkv, float* __restrict__ dx, float* __restrict__ dvs,
                                   int B, int Hh, int Ww, int G, int J, int PD) {
@@ -453,7 +454,7 @@ __global__ void sample_bwd_kernel(const float* __restrict__ x, const float* __re
   const float go = live ? dkv[id] : 0.f;
   const float wx1 = k.fx, wx0 = 1.f - k.fx, wy1 = k.fy, wy0 = 1.f - k.fy;
   const float v00 = m00 ? x[i00] : 0.f, v10 = m10 ? x[i10] : 0.f, v01 = m01 ? x[i01] : 0.f, v11 = m11 ? x[i11] : 0.f;
-  if (live) {
+  if (SCATTER && live) {
     if (m00) atomicAdd(&dx[i00], go * (wx0 * wy0));
     if (m10) atomicAdd(&dx[i10], go * (wx1 * wy0));
     if (m01) atomicAdd(&dx[i01], go * (wx0 * wy1));
@@ -472,6 +473,90 @@ __global__ void sample_bwd_kernel(const float* __restrict__ x, const float* __re
     d[0] += gx;
     if (PD == 2) d[1] += gy;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// deterministic sampling backward: dx as a gather.  Per (bag, group) the 4 J contributions (pixel, key j, corner) are sorted by the key
+//   pixel * 2^14 + (4 j + corner)            (corners outside the map: pixel = Hh Ww, a run nobody reads)
+// - the keys are unique, so the sorted order is a property of the data alone - and every (pixel, channel) then adds its pixel's run in that
+// order.  Indices and masks come from corners_of() as in the scatter kernel, the weights are that kernel's expressions.
+// ---------------------------------------------------------------------------------------------
+constexpr int SBD_KEYBITS = 14, SBD_MAXJ = 1 << (SBD_KEYBITS - 2);     // 4 J <= 16384 keys: a 64 KB bitonic sort in LDS
+constexpr int SBD_MAXPIX = (1 << (32 - SBD_KEYBITS)) - 2;              // every real key stays below the padding key 0xFFFFFFFF
+constexpr int SBD_THREADS = 512;
+
+// one workgroup per (bag, group): build the P = 2^ceil(log2(4 J)) keys in LDS, bitonic sort, then the sorted keys [4 J] and, per pixel
+// p = 0 .. Hh Ww, start[p] = index of the first key of pixel p or later (binary search).  Every __syncthreads() sits in uniform control
+// flow: the trip counts of the loops around them depend on P alone.
+__global__ __launch_bounds__(SBD_THREADS) void sample_bwd_sort_kernel(const float* __restrict__ vs, unsigned* __restrict__ keys,
+                                                                      unsigned* __restrict__ start, int Hh, int Ww, int J, int PD, int P) {
+  extern __shared__ unsigned skey[];
+  const int bg = blockIdx.x, tid = threadIdx.x;
+  const int n = 4 * J, HW = Hh * Ww;
+  for (int i = tid; i < P; i += SBD_THREADS) {
+    unsigned key = 0xFFFFFFFFu;
+    if (i < n) {
+      const int j = i >> 2, cn = i & 3;                    // corner order of the scatter kernel: (x0,y0) (x1,y0) (x0,y1) (x1,y1)
+      const float* p = vs + ((size_t)bg * J + j) * PD;
+      const Corners k = corners_of(p[0], (PD == 2) ? p[1] : 0.f, Ww, Hh);
+      const bool mx = (cn & 1) ? k.mx1 : k.mx0, my = (cn & 2) ? k.my1 : k.my0;
+      const int pix = (mx && my) ? (k.y0 + (cn >> 1)) * Ww + k.x0 + (cn & 1) : HW;
+      key = ((unsigned)pix << SBD_KEYBITS) | (unsigned)i;
+    }
+    skey[i] = key;
+  }
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P >> 1); t += SBD_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+        const unsigned a = skey[i], b = skey[l];
+        const bool up = (i & k) == 0;
+        if ((a > b) == up) { skey[i] = b; skey[l] = a; }
+      }
+      __syncthreads();
+    }
+  unsigned* kout = keys + (size_t)bg * n;
+  for (int i = tid; i < n; i += SBD_THREADS) kout[i] = skey[i];
+  unsigned* sout = start + (size_t)bg * (HW + 1);
+  for (int p = tid; p <= HW; p += SBD_THREADS) {
+    const unsigned target = (unsigned)p << SBD_KEYBITS;
+    int lo = 0, hi = n;                                    // first index whose key is >= target
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (skey[mid] < target) lo = mid + 1; else hi = mid;
+    }
+    sout[p] = (unsigned)lo;
+  }
+}
+
+// thread per (b, pixel, channel): dx = sum over the pixel's run, in sorted order, of dkv[b, j, ch] * (corner weight); 0 for an empty run
+template <int CG>
+__global__ __launch_bounds__(256) void sample_bwd_gather_kernel(const float* __restrict__ vs, const float* __restrict__ dkv,
+                                                                const unsigned* __restrict__ keys, const unsigned* __restrict__ start,
+                                                                float* __restrict__ dx, int B, int Hh, int Ww, int G, int J, int PD) {
+  const int C = G * CG, HW = Hh * Ww;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)B * HW * C) return;
+  const int ch = (int)(idx % C);
+  const size_t bp = idx / C;
+  const int pix = (int)(bp % HW), b = (int)(bp / HW);
+  const int bg = b * G + ch / CG;
+  const unsigned* st = start + (size_t)bg * (HW + 1) + pix;
+  const unsigned s0 = st[0], s1 = st[1];
+  const unsigned* kk = keys + (size_t)bg * 4 * J;
+  const float* vp = vs + (size_t)bg * J * PD;
+  const float* dk = dkv + (size_t)b * J * C + ch;
+  float acc = 0.f;
+#pragma unroll 4
+  for (unsigned i = s0; i < s1; ++i) {
+    const unsigned slot = kk[i] & ((1u << SBD_KEYBITS) - 1u);
+    const int j = (int)(slot >> 2), cn = (int)(slot & 3u);
+    const Corners k = corners_of(vp[(size_t)j * PD], (PD == 2) ? vp[(size_t)j * PD + 1] : 0.f, Ww, Hh);
+    const float wx = (cn & 1) ? k.fx : 1.f - k.fx, wy = (cn & 2) ? k.fy : 1.f - k.fy;
+    acc += dk[(size_t)j * C] * (wx * wy);
+  }
+  dx[idx] = acc;
 }
 
 __global__ void corners_kernel(const float* __restrict__ vs, int* __restrict__ cx, int* __restrict__ cy,
@@ -640,6 +725,49 @@ int smml_bilinear_sample_bwd_f32(const float* x, const float* vs, const float* d
     hipLaunchKernelGGL(sample_bwd_kernel<32>, grid, block, 0, (hipStream_t)stream, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J,
                        posdim);
   SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_f32");
+  return SMML_OK;
+}
+
+// scratch of the deterministic backward: sorted keys [(B G)][4 J] + run starts [(B G)][Hh Ww + 1], 4 bytes each
+size_t smml_bilinear_sample_bwd_det_workspace_bytes(int B, int Hh, int Ww, int G, int J) {
+  if (B <= 0 || Hh <= 0 || Ww <= 0 || G <= 0 || J <= 0) return 0;
+  return (size_t)B * (size_t)G * (4 * (size_t)J + (size_t)Hh * (size_t)Ww + 1) * sizeof(unsigned);
+}
+
+// dx is OVERWRITTEN (a gather in a fixed order: no atomics, pixels nobody samples get 0); dvs is accumulated into (+=) with the arithmetic of
+// smml_bilinear_sample_bwd_f32.  J <= 4096, Hh Ww <= 262142.
+int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const float* dkv, float* dx, float* dvs, void* workspace,
+                                     size_t workspace_bytes, int B, int Hh, int Ww, int G, int cg, int J, int posdim, void* stream) {
+  SMML_REQUIRE(x && vs && dkv && dx && dvs && workspace, "smml_bilinear_sample_bwd_det_f32: null pointer");
+  SMML_REQUIRE(posdim == 1 || posdim == 2, "smml_bilinear_sample_bwd_det_f32: posdim must be 1 or 2");
+  SMML_REQUIRE(cg == 16 || cg == 32, "smml_bilinear_sample_bwd_det_f32: channels per group must be 16 or 32 (got %d)", cg);
+  SMML_REQUIRE(B > 0 && Hh > 0 && Ww > 0 && G > 0 && J > 0, "smml_bilinear_sample_bwd_det_f32: bad size");
+  SMML_REQUIRE(J <= SBD_MAXJ, "smml_bilinear_sample_bwd_det_f32: %d keys (the deterministic sampler backward sorts at most %d)", J, SBD_MAXJ);
+  SMML_REQUIRE((long long)Hh * Ww <= SBD_MAXPIX, "smml_bilinear_sample_bwd_det_f32: %lld pixels (at most %d)", (long long)Hh * Ww, SBD_MAXPIX);
+  SMML_REQUIRE((long long)B * G <= 2147483647LL, "smml_bilinear_sample_bwd_det_f32: too many (bag, group) pairs");
+  SMML_REQUIRE(workspace_bytes >= smml_bilinear_sample_bwd_det_workspace_bytes(B, Hh, Ww, G, J),
+               "smml_bilinear_sample_bwd_det_f32: workspace too small");
+  const size_t n = (size_t)B * J * G * cg, nx = (size_t)B * Hh * Ww * G * cg;
+  SMML_REQUIRE((n + 255) / 256 <= 2147483647ULL && (nx + 255) / 256 <= 2147483647ULL, "smml_bilinear_sample_bwd_det_f32: too many elements");
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* keys = (unsigned*)workspace;
+  unsigned* start = keys + (size_t)B * G * 4 * J;
+  int P = 4;
+  while (P < 4 * J) P <<= 1;
+  dim3 grid((unsigned)((n + 255) / 256)), gridx((unsigned)((nx + 255) / 256)), block(256);
+  if (cg == 16)
+    hipLaunchKernelGGL((sample_bwd_kernel<16, false>), grid, block, 0, st, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J, posdim);
+  else
+    hipLaunchKernelGGL((sample_bwd_kernel<32, false>), grid, block, 0, st, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J, posdim);
+  SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/dvs");
+  hipLaunchKernelGGL(sample_bwd_sort_kernel, dim3((unsigned)(B * G)), dim3(SBD_THREADS), (size_t)P * sizeof(unsigned), st, vs, keys, start,
+                     Hh, Ww, J, posdim, P);
+  SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/sort");
+  if (cg == 16)
+    hipLaunchKernelGGL(sample_bwd_gather_kernel<16>, gridx, block, 0, st, vs, dkv, keys, start, dx, B, Hh, Ww, G, J, posdim);
+  else
+    hipLaunchKernelGGL(sample_bwd_gather_kernel<32>, gridx, block, 0, st, vs, dkv, keys, start, dx, B, Hh, Ww, G, J, posdim);
+  SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/gather");
   return SMML_OK;
 }
 

@@ -5,7 +5,7 @@
 // LayerNorm: the generic kernels put one wave on one row (lane l owns columns l, l + 64, ...; C <= 1024); at C = 128 - the path's token
 // width - that is one 512-byte row in flight per wave and latency-bound, so both directions have a 128-column kernel: a half-wave per
 // row, one float4 per lane, several rows of loads in flight per wave, grid-stride loop.  Partial column sums leave a workgroup
-// through float atomics.
+// through float atomics, or - the deterministic entry points - as a row of a partial slab that is summed in a fixed order.
 #include <algorithm>
 #include "smml_common.h"
 
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             const float* __restrict__ rstd, float* __restrict__ dx,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                             long long R, int C, long long rows_per_dy, float dy_scale,
-                                                            int accumulate_dx) {
+                                                            int accumulate_dx, float* __restrict__ part) {
   __shared__ float red[2][4][64 * MAXV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv = (C + 63) >> 6;
@@ -171,8 +171,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   for (int c = threadIdx.x; c < C; c += 256) {
     const float g = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
     const float b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
-    atomicAdd(&dgamma[c], g);
-    atomicAdd(&dbeta[c], b);
+    if (part) {        // deterministic mode: this workgroup's row of the slab [workgroup][2][C]; slab_reduce_kernel adds the rows in a fixed order
+      part[((size_t)blockIdx.x * 2 + 0) * C + c] = g;
+      part[((size_t)blockIdx.x * 2 + 1) * C + c] = b;
+    } else {
+      atomicAdd(&dgamma[c], g);
+      atomicAdd(&dbeta[c], b);
+    }
   }
 }
 
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd128_kernel(const float* __re
                                                                const float* __restrict__ rstd, float* __restrict__ dx,
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                long long R, long long rows_per_dy, float dy_scale,
-                                                               int accumulate_dx) {
+                                                               int accumulate_dx, float* __restrict__ part) {
   constexpr int C = 128;
   __shared__ float red[2][8][C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
@@ -239,14 +244,20 @@ __global__ __launch_bounds__(256) void layernorm_bwd128_kernel(const float* __re
     float g = 0.f, bsum = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { g += red[0][i][threadIdx.x]; bsum += red[1][i][threadIdx.x]; }
-    atomicAdd(&dgamma[threadIdx.x], g);
-    atomicAdd(&dbeta[threadIdx.x], bsum);
+    if (part) {        // deterministic mode (see layernorm_bwd_kernel)
+      part[((size_t)blockIdx.x * 2 + 0) * C + threadIdx.x] = g;
+      part[((size_t)blockIdx.x * 2 + 1) * C + threadIdx.x] = bsum;
+    } else {
+      atomicAdd(&dgamma[threadIdx.x], g);
+      atomicAdd(&dbeta[threadIdx.x], bsum);
+    }
   }
 }
 
 // out[b, c] += scale * sum_{r in chunk} x[b, r, c]   (x [nb, R, C] contiguous; out zeroed by the caller)
+// part != NULL (deterministic mode): the chunk's scaled sums are stored to part[chunk][b][C] instead; slab_reduce_kernel adds the chunks
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, float* __restrict__ out, long long R,
-                                                     int C, float scale, int rows_per_block) {
+                                                     int C, float scale, int rows_per_block, float* __restrict__ part) {
   __shared__ float red[256];
   const int b = blockIdx.y;
   const long long r0 = (long long)blockIdx.x * rows_per_block;
@@ -269,7 +280,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
     if (threadIdx.x < cp && threadIdx.x < ncol) {
       float t = 0.f;
       for (int k = 0; k < rl; ++k) t += red[k * cp + threadIdx.x];
-      atomicAdd(&out[(long long)b * C + cb + threadIdx.x], t * scale);
+      if (part) part[((size_t)blockIdx.x * gridDim.y + b) * C + cb + threadIdx.x] = t * scale;
+      else atomicAdd(&out[(long long)b * C + cb + threadIdx.x], t * scale);
     }
     __syncthreads();
   }
@@ -279,7 +291,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
 // every (256 / (C / 4))-th row of its block's chunk, eight loads in flight per thread (the scalar form above read 41 MB in 26 us
 // = 1.6 TB/s; this one is HBM-paced)
 __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ x, float* __restrict__ out, long long R, int C,
-                                                      float scale, int rows_per_block) {
+                                                      float scale, int rows_per_block, float* __restrict__ part) {
   __shared__ float4 red[256];
   const int b = blockIdx.y;
   const int cq = C >> 2;                               // float4 columns (<= 256)
@@ -306,8 +318,36 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ 
   if (threadIdx.x < cq) {
     float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int k = 0; k < rl; ++k) { const float4 v = red[k * cq + threadIdx.x]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-    float* o = out + (long long)b * C + 4 * threadIdx.x;
-    atomicAdd(o, t.x * scale); atomicAdd(o + 1, t.y * scale); atomicAdd(o + 2, t.z * scale); atomicAdd(o + 3, t.w * scale);
+    if (part) {
+      *reinterpret_cast<float4*>(part + ((size_t)blockIdx.x * gridDim.y + b) * C + 4 * threadIdx.x) =
+          make_float4(t.x * scale, t.y * scale, t.z * scale, t.w * scale);
+    } else {
+      float* o = out + (long long)b * C + 4 * threadIdx.x;
+      atomicAdd(o, t.x * scale); atomicAdd(o + 1, t.y * scale); atomicAdd(o + 2, t.z * scale); atomicAdd(o + 3, t.w * scale);
+    }
+  }
+}
+
+// Fixed-order column sums of a partial slab [nrows][ncols] (the deterministic forms of the LayerNorm backward and of the column sums): a
+// workgroup owns 32 columns; row lane l of 8 adds rows l, l + 8, ... in ascending order, then one thread per column adds the eight lane sums,
+// lane 0 first.  Column c goes to out0[c] (c < split) or out1[c - split]; add: the sum is added onto what is there (dgamma / dbeta are
+// accumulated into), else it is stored.
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ part, long long nrows, long long ncols,
+                                                          float* __restrict__ out0, float* __restrict__ out1, long long split, int add) {
+  __shared__ float red[8][32];
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const long long c = (long long)blockIdx.x * 32 + cl;
+  float s = 0.f;
+  if (c < ncols)
+    for (long long r = rl; r < nrows; r += 8) s += part[r * ncols + c];
+  red[rl][cl] = s;
+  __syncthreads();
+  if (rl == 0 && c < ncols) {
+    float t = red[0][cl];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) t += red[k][cl];
+    float* o = c < split ? out0 + c : out1 + (c - split);
+    *o = add ? *o + t : t;
   }
 }
 
@@ -449,10 +489,10 @@ int smml_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, 
   if (C == 128 && aligned) {
     const long long nb16 = (R + 15) / 16;
     hipLaunchKernelGGL(layernorm_bwd128_kernel, dim3((unsigned)(nb16 < 768 ? nb16 : 768)), dim3(256), 0, (hipStream_t)stream,
-                       x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, rows_per_dy, dy_scale, accumulate_dx);
+                       x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, rows_per_dy, dy_scale, accumulate_dx, (float*)nullptr);
   } else
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)(nblk < 1024 ? nblk : 1024)), dim3(256), 0, (hipStream_t)stream,
-                     x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, C, rows_per_dy, dy_scale, accumulate_dx);
+                     x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, C, rows_per_dy, dy_scale, accumulate_dx, (float*)nullptr);
   SMML_LAUNCH_CHECK("smml_layernorm_bwd_f32");
   return SMML_OK;
 }
@@ -467,15 +507,92 @@ int smml_colsum_f32(const float* x, float* out, int nb, long long R, int C, floa
     long long rpb = std::max<long long>(64LL * rl, (R * nb + 2047) / 2048);
     rpb = (rpb + rl - 1) / rl * rl;
     const long long nb4 = (R + rpb - 1) / rpb;
-    hipLaunchKernelGGL(colsum4_kernel, dim3((unsigned)nb4, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, R, C, scale, (int)rpb);
+    hipLaunchKernelGGL(colsum4_kernel, dim3((unsigned)nb4, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, R, C, scale, (int)rpb, (float*)nullptr);
     SMML_LAUNCH_CHECK("smml_colsum_f32/4");
     return SMML_OK;
   }
   int rows_per_block = 256;
   long long nblk = (R + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)nblk, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, R, C,
-                     scale, rows_per_block);
+                     scale, rows_per_block, (float*)nullptr);
   SMML_LAUNCH_CHECK("smml_colsum_f32");
+  return SMML_OK;
+}
+
+// ---- deterministic forms: partial rows to a caller-allocated workspace with plain stores, then slab_reduce_kernel (no float atomics)
+// workgroups of the LayerNorm backward - a function of (R, C) alone: the 128-column kernel's grid at C = 128, else the generic kernel's
+static long long layernorm_bwd_det_workgroups(long long R, int C) {
+  if (C == 128) { const long long nb16 = (R + 15) / 16; return nb16 < 768 ? nb16 : 768; }
+  const long long nblk = (R + 3) / 4;
+  return nblk < 1024 ? nblk : 1024;
+}
+
+size_t smml_layernorm_bwd_det_workspace_bytes(long long R, int C) {
+  if (R <= 0 || C <= 0 || C > 64 * MAXV) return 0;
+  return (size_t)layernorm_bwd_det_workgroups(R, C) * 2 * (size_t)C * sizeof(float);
+}
+
+// smml_layernorm_bwd_f32 with dgamma / dbeta summed in a fixed order (added onto what they hold, as there); dx is that entry point's, bit for bit
+int smml_layernorm_bwd_det_f32(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd,
+                               float* dx, float* dgamma, float* dbeta, long long R, int C, long long rows_per_dy,
+                               float dy_scale, int accumulate_dx, void* workspace, size_t workspace_bytes, void* stream) {
+  SMML_REQUIRE(x && dy && gamma && mean && rstd && dx && dgamma && dbeta && workspace, "smml_layernorm_bwd_det_f32: null pointer");
+  SMML_REQUIRE(R > 0 && C > 0 && C <= 64 * MAXV, "smml_layernorm_bwd_det_f32: need 0 < C <= %d (got %d)", 64 * MAXV, C);
+  SMML_REQUIRE(rows_per_dy >= 1, "smml_layernorm_bwd_det_f32: rows_per_dy must be >= 1");
+  SMML_REQUIRE(workspace_bytes >= smml_layernorm_bwd_det_workspace_bytes(R, C), "smml_layernorm_bwd_det_f32: workspace too small");
+  const long long nwg = layernorm_bwd_det_workgroups(R, C);
+  float* part = (float*)workspace;
+  const bool aligned = ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(dy) | reinterpret_cast<size_t>(dx) |
+                         reinterpret_cast<size_t>(gamma)) & 15) == 0;
+  if (C == 128 && aligned)
+    hipLaunchKernelGGL(layernorm_bwd128_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream,
+                       x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, rows_per_dy, dy_scale, accumulate_dx, part);
+  else
+    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream,
+                       x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, C, rows_per_dy, dy_scale, accumulate_dx, part);
+  SMML_LAUNCH_CHECK("smml_layernorm_bwd_det_f32");
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, (hipStream_t)stream, part, nwg, (long long)2 * C,
+                     dgamma, dbeta, (long long)C, 1);
+  SMML_LAUNCH_CHECK("smml_layernorm_bwd_det_f32/reduce");
+  return SMML_OK;
+}
+
+// rows per chunk of the deterministic column sums - a function of (R, C) alone (smml_colsum_f32 also looks at the batch count): the
+// float4 kernel's chunk where C allows it (at least 64 rows per row lane, at most ~2048 chunks), else 256 rows
+static long long colsum_det_rows_per_chunk(long long R, int C) {
+  if ((C & 3) == 0 && C <= 1024 && 256 % (C >> 2) == 0) {
+    const int rl = 256 / (C >> 2);
+    const long long rpb = std::max<long long>(64LL * rl, (R + 2047) / 2048);
+    return (rpb + rl - 1) / rl * rl;
+  }
+  return 256;
+}
+
+size_t smml_colsum_det_workspace_bytes(int nb, long long R, int C) {
+  if (nb <= 0 || R <= 0 || C <= 0) return 0;
+  const long long rpc = colsum_det_rows_per_chunk(R, C);
+  return (size_t)((R + rpc - 1) / rpc) * (size_t)nb * (size_t)C * sizeof(float);
+}
+
+// out[b, c] = scale * sum_r x[b, r, c], overwritten: chunk sums to the workspace [chunks][nb][C], then a fixed-order sum over the chunks
+int smml_colsum_det_f32(const float* x, float* out, int nb, long long R, int C, float scale, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  SMML_REQUIRE(x && out && workspace && nb > 0 && R > 0 && C > 0, "smml_colsum_det_f32: bad argument");
+  SMML_REQUIRE(nb <= 65535, "smml_colsum_det_f32: too many batches");
+  SMML_REQUIRE(workspace_bytes >= smml_colsum_det_workspace_bytes(nb, R, C), "smml_colsum_det_f32: workspace too small");
+  const long long rpc = colsum_det_rows_per_chunk(R, C), chunks = (R + rpc - 1) / rpc;
+  SMML_REQUIRE(rpc <= 2147483647LL && chunks <= 2147483647LL, "smml_colsum_det_f32: too many rows");
+  float* part = chunks == 1 ? out : (float*)workspace;      // a single chunk is the result itself ([1][nb][C]): no second pass
+  if ((C & 3) == 0 && C <= 1024 && 256 % (C >> 2) == 0 && (((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(part)) & 15) == 0))
+    hipLaunchKernelGGL(colsum4_kernel, dim3((unsigned)chunks, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, R, C, scale, (int)rpc, part);
+  else
+    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)chunks, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, R, C, scale, (int)rpc, part);
+  SMML_LAUNCH_CHECK("smml_colsum_det_f32");
+  if (chunks == 1) return SMML_OK;
+  const long long ncols = (long long)nb * C;
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((ncols + 31) / 32)), dim3(256), 0, (hipStream_t)stream, part, chunks, ncols, out,
+                     out, ncols, 0);
+  SMML_LAUNCH_CHECK("smml_colsum_det_f32/reduce");
   return SMML_OK;
 }
 

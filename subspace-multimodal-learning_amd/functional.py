@@ -18,6 +18,63 @@ from . import _capi as capi
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 
 
+# ------------------------------------------------------------------------------------------------
+# Deterministic mode: with the switch on, every sum the package's kernels form runs in a fixed order - partial results
+# to a workspace, one owner per output element - so a value or gradient is a function of the inputs alone, run after run.  Off (the
+# default) nothing changes: the same kernels, launches and bits as without the switch.  SMML_DETERMINISTIC=1 presets it.
+# ------------------------------------------------------------------------------------------------
+DETERMINISTIC = os.environ.get("SMML_DETERMINISTIC", "0") not in ("", "0")
+
+
+def set_deterministic(on: bool) -> None:
+    """Switches the deterministic mode on or off for the calls that follow (see `deterministic`)."""
+    global DETERMINISTIC
+    DETERMINISTIC = bool(on)
+
+
+def is_deterministic() -> bool:
+    return bool(DETERMINISTIC)
+
+
+class deterministic:
+    """with deterministic(): ... - the deterministic mode for the forward calls issued inside the block; nests, and restores the previous
+    value on exit, also when the block raises.  Every autograd Function reads the switch in its FORWARD and keeps the choice: its backward
+    is deterministic as well, even when it runs after the block has ended.
+
+    Covered: the fp32-grade and 16-bit deform paths (DeformPathomicNet, both attn_dim values), BatchLoss and the co-attention
+    MultiheadAttention.  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
+    bf16-storage GEMM with a split reduction, the depthwise-convolution weight gradients of the Nystrom block and of PPEG - raises
+    RuntimeError under the switch; there is no silent fall-back.
+
+    The switch is NOT tied to torch.use_deterministic_algorithms: that flag makes unrelated ATen operations raise, and this package's
+    kernels do not read it.  Set both if the ATen side of a program has to be pinned down too."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+        self.prev = []
+
+    def __enter__(self):
+        global DETERMINISTIC
+        self.prev.append(DETERMINISTIC)
+        DETERMINISTIC = self.on
+        return self
+
+    def __exit__(self, *exc):
+        global DETERMINISTIC
+        DETERMINISTIC = self.prev.pop()
+        return False
+
+
+def _no_det(op: str, why: str):
+    raise RuntimeError(f"{op} has no deterministic form yet: {why} (functional.deterministic / SMML_DETERMINISTIC is on; "
+                       "there is no silent fall-back)")
+
+
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """Workspace of a deterministic launch: a plain torch.empty tensor (16-byte aligned, no host synchronisation, graph-capturable)."""
+    return torch.empty(max((int(nbytes) + 3) // 4, 1), device=device, dtype=torch.float32)
+
+
 class KernelTimer:
     """Optional HIP-event timing of the two dominant kernels (fused attention forward, position-bias
     backward) on the stream they are launched on; used by bench.py's roofline leg.  Off by default."""
@@ -130,7 +187,17 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 def _gemm(A, B, C, *, M, N, K, sam, sak, sbk, sbn, ldc, bias=None, bias_mode=0, rows_per_bias=1, bias_ld=0,
           residual=None, ldr=0, act=ACT_NONE, splitk=1, alpha=1.0, nb0=1, nb1=1, sa0=0, sa1=0, sb0=0, sb1=0,
-          sc0=0, sc1=0, sbias0=0, sbias1=0, beta=1.0, accumulate=0):
+          sc0=0, sc1=0, sbias0=0, sbias1=0, beta=1.0, accumulate=0, det=False):
+    """det (the caller's deterministic choice, taken in its forward): products whose slices or batch items add up in one C (splitk > 1 or
+    accumulate) go through smml_gemm_f32_det, which OVERWRITES C with the fixed-order sum - the caller need not zero it."""
+    if det and (splitk > 1 or accumulate):
+        L = capi.lib()
+        wsb = L.smml_gemm_f32_det_workspace_bytes(M, N, nb0, nb1, splitk)
+        ws = _scratch(wsb, C.device)
+        capi.check(L.smml_gemm_f32_det(
+            capi.fptr(A), capi.fptr(B), capi.fptr(C), None, None, M, N, K, sam, sak, sbk, sbn, ldc, 0, nb0, nb1, sa0, sa1, sb0, sb1, sc0, sc1,
+            0, 0, 0, 1, 0, 0, splitk, 0, float(alpha), 1.0, capi.fptr(ws), wsb, capi.stream()), "gemm (deterministic)")
+        return
     capi.check(capi.lib().smml_gemm_f32(
         capi.fptr(A), capi.fptr(B), capi.fptr(C), capi.fptr(bias), capi.fptr(residual), M, N, K,
         sam, sak, sbk, sbn, ldc, ldr, nb0, nb1, sa0, sa1, sb0, sb1, sc0, sc1, sbias0, sbias1,
@@ -160,10 +227,18 @@ def _splitk_for(out_rows: int, out_cols: int, k: int, batches: int = 1) -> int:
     return int(max(1, min(want, (k + 255) // 256, 65535 // max(batches, 1))))
 
 
-def colsum(x2d_or_3d: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
-    """x [nb, R, C] -> [nb, C] column sums * scale."""
+def colsum(x2d_or_3d: torch.Tensor, scale: float = 1.0, det: Optional[bool] = None) -> torch.Tensor:
+    """x [nb, R, C] -> [nb, C] column sums * scale.  det: the deterministic choice of the calling Function (None: the switch as it stands)."""
     x = x2d_or_3d
     nb, R, Cc = x.shape
+    if DETERMINISTIC if det is None else det:
+        L = capi.lib()
+        out = torch.empty(nb, Cc, device=x.device, dtype=torch.float32)
+        wsb = L.smml_colsum_det_workspace_bytes(nb, R, Cc)
+        ws = _scratch(wsb, x.device)
+        capi.check(L.smml_colsum_det_f32(capi.fptr(x), capi.fptr(out), nb, R, Cc, float(scale), capi.fptr(ws), wsb, capi.stream()),
+                   "colsum (deterministic)")
+        return out
     out = _ZEROS.zeros((nb, Cc), x.device)
     capi.check(capi.lib().smml_colsum_f32(capi.fptr(x), capi.fptr(out), nb, R, Cc, float(scale), capi.stream()), "colsum")
     return out
@@ -176,6 +251,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, rows_per_bias, residual, prec=0):
         x = _c(x); weight = _c(weight)
+        ctx.det = DETERMINISTIC
         ctx.prec = 3 if prec == 4 else prec          # fp16 operands are for forward-range values: the gradient products of mode 4 run in bf16
         K = x.shape[-1]
         M = x.numel() // K
@@ -216,13 +292,13 @@ class _Linear(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 _gemm(dpre, weight, dx, M=M, N=K, K=N, sam=N, sak=1, sbk=K, sbn=1, ldc=K)
             if ctx.needs_input_grad[1]:
-                dw = _zeros_like(weight)
-                _gemm(dpre, x, dw, M=N, N=K, K=M, sam=1, sak=N, sbk=K, sbn=1, ldc=K, splitk=_splitk_for(N, K, M))
+                dw = torch.empty_like(weight) if ctx.det else _zeros_like(weight)
+                _gemm(dpre, x, dw, M=N, N=K, K=M, sam=1, sak=N, sbk=K, sbn=1, ldc=K, splitk=_splitk_for(N, K, M), det=ctx.det)
         if ctx.bias_mode and ctx.needs_input_grad[2]:
             if ctx.bias_mode == 1:
-                db = colsum(dpre.reshape(1, M, N))[0]
+                db = colsum(dpre.reshape(1, M, N), det=ctx.det)[0]
             else:
-                db = colsum(dpre.reshape(M // ctx.rows_per_bias, ctx.rows_per_bias, N))
+                db = colsum(dpre.reshape(M // ctx.rows_per_bias, ctx.rows_per_bias, N), det=ctx.det)
         return dx, dw, db, None, None, dres, None
 
 
@@ -241,6 +317,7 @@ class _DualLinearRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w0, b0, w1, b1):
         x = _c(x)
+        ctx.det = DETERMINISTIC
         K = x.shape[-1]
         M = x.numel() // K
         N = w0.shape[0]
@@ -265,10 +342,10 @@ class _DualLinearRelu(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             raise RuntimeError("dual_linear_relu: the shared input is a bag of features (no gradient path is built)")
-        dw = _ZEROS.zeros((2, N, K), x.device)
+        dw = torch.empty(2, N, K, device=x.device, dtype=torch.float32) if ctx.det else _ZEROS.zeros((2, N, K), x.device)
         _gemm(dpre, x, dw, M=N, N=K, K=M, sam=1, sak=N, sbk=K, sbn=1, ldc=K, nb1=2, sa1=M * N, sb1=0, sc1=N * K,
-              splitk=_splitk_for(N, K, M, 2))
-        db = colsum(dpre.reshape(2, M, N))
+              splitk=_splitk_for(N, K, M, 2), det=ctx.det)
+        db = colsum(dpre.reshape(2, M, N), det=ctx.det)
         return dx, dw[0], db[0], dw[1], db[1]
 
 
@@ -304,6 +381,7 @@ class _LinearB16(torch.autograd.Function):
     def forward(ctx, x, weight, bias, out_bf16, skip):
         if x.dtype != torch.bfloat16:
             raise RuntimeError("linear_b16: x must be bf16 (the caller casts once)")
+        ctx.det = DETERMINISTIC
         x = x if x.is_contiguous() else x.contiguous()
         wb = weight.detach().to(torch.bfloat16)                 # the parameter stays fp32; [N, K] bf16 is 1.5 MB at most here
         K = x.shape[-1]
@@ -330,10 +408,13 @@ class _LinearB16(torch.autograd.Function):
         K = x.shape[-1]
         N = wb.shape[0]
         skip = ctx.skip
+        if ctx.det and ctx.needs_input_grad[1]:
+            _no_det("linear_b16 backward (weight gradient)", "the bf16-storage GEMM adds the slices of its split reduction with float atomics "
+                    "(smml_gemm_b16 / smml_gemm_b16_batched)")
         rows_y = dy.numel() // N
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = colsum(_c(dy).reshape(1, rows_y, N))[0]
+            db = colsum(_c(dy).reshape(1, rows_y, N), det=ctx.det)[0]
         dyb = dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16)
         dyb = dyb if dyb.is_contiguous() else dyb.contiguous()
         dx = dw = None
@@ -399,6 +480,7 @@ class _QKVProject16(torch.autograd.Function):
     def forward(ctx, x, weight, heads, l, pad):
         if x.dtype != torch.bfloat16:
             raise RuntimeError("qkv_project16: x must be bf16")
+        ctx.det = DETERMINISTIC
         x = x if x.is_contiguous() else x.contiguous()
         wb = weight.detach().to(torch.bfloat16)
         b, n0, K = x.shape
@@ -421,6 +503,9 @@ class _QKVProject16(torch.autograd.Function):
     def backward(ctx, dqkv, dql, dkl):
         x, wb = ctx.saved_tensors
         heads, l, d, pad = ctx.cfg
+        if ctx.det and ctx.needs_input_grad[1]:
+            _no_det("qkv_project16 backward (weight gradient)", "the bf16-storage GEMM adds the slices of its split reduction with float "
+                    "atomics (smml_gemm_b16_batched)")
         b, n0, K = x.shape
         n = n0 + pad
         N = wb.shape[0]
@@ -510,6 +595,7 @@ class _ResConv16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, w, heads):
         b, n, c, d = _qkv_dims(qkv, heads)
+        ctx.det = DETERMINISTIC
         hd = heads * d
         kw = w.shape[2]
         w2 = _c(w.reshape(heads, kw))
@@ -524,6 +610,9 @@ class _ResConv16(torch.autograd.Function):
     def backward(ctx, dres, dqkv):
         qkv, w2 = ctx.saved_tensors
         heads, kw, wshape = ctx.cfg
+        if ctx.det and dres is not None and ctx.needs_input_grad[1]:
+            _no_det("resconv16 backward (weight gradient)", "the depthwise-convolution weight gradient of the Nystrom block is summed with "
+                    "float atomics (smml_resconv_wgrad_b16)")
         b, n, c, d = _qkv_dims(qkv, heads)
         hd = heads * d
         if dqkv is None:
@@ -634,6 +723,7 @@ class _GroupedPointwise(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, groups):
         x = _c(x)
+        ctx.det = DETERMINISTIC
         w = _c(weight).reshape(weight.shape[0], -1)
         Cin, Cout = x.shape[-1], w.shape[0]
         cin_g, cout_g = Cin // groups, Cout // groups
@@ -661,9 +751,9 @@ class _GroupedPointwise(torch.autograd.Function):
             _gemm(dy, w, dx, M=M, N=cin_g, K=cout_g, sam=Cout, sak=1, sbk=cin_g, sbn=1, ldc=Cin, nb1=G,
                   sa1=cout_g, sb1=cout_g * cin_g, sc1=cin_g)
         if ctx.needs_input_grad[1]:
-            dw = _zeros_like(w)
+            dw = torch.empty_like(w) if ctx.det else _zeros_like(w)
             _gemm(dy, x, dw, M=cout_g, N=cin_g, K=M, sam=1, sak=Cout, sbk=Cin, sbn=1, ldc=cin_g, nb1=G,
-                  sa1=cout_g, sb1=cin_g, sc1=cout_g * cin_g, splitk=_splitk_for(cout_g, cin_g, M, G))
+                  sa1=cout_g, sb1=cin_g, sc1=cout_g * cin_g, splitk=_splitk_for(cout_g, cin_g, M, G), det=ctx.det)
             dw = dw.reshape(ctx.wshape)
         return dx, dw, None
 
@@ -688,10 +778,11 @@ class _LayerNorm(torch.autograd.Function):
                                                      capi.fptr(mean), capi.fptr(rstd), R, Cc, float(eps),
                                                      capi.stream()), "layernorm_fwd")
         ctx.token_mean = token_mean
+        ctx.det = DETERMINISTIC
         ctx.save_for_backward(x, gamma, mean, rstd)
         if token_mean:
             assert x.dim() == 3
-            return colsum(y, 1.0 / x.shape[1])
+            return colsum(y, 1.0 / x.shape[1], det=ctx.det)
         return y
 
     @staticmethod
@@ -704,6 +795,14 @@ class _LayerNorm(torch.autograd.Function):
         dg = _zeros_like(gamma)
         db = _zeros_like(gamma)
         rows_per_dy, scale = (x.shape[1], 1.0 / x.shape[1]) if ctx.token_mean else (1, 1.0)
+        if ctx.det:
+            L = capi.lib()
+            wsb = L.smml_layernorm_bwd_det_workspace_bytes(R, Cc)
+            ws = _scratch(wsb, x.device)
+            capi.check(L.smml_layernorm_bwd_det_f32(capi.fptr(x), capi.fptr(dy), capi.fptr(gamma), capi.fptr(mean), capi.fptr(rstd),
+                                                    capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc, rows_per_dy, float(scale), 0,
+                                                    capi.fptr(ws), wsb, capi.stream()), "layernorm_bwd (deterministic)")
+            return dx, dg, db, None, None
         capi.check(capi.lib().smml_layernorm_bwd_f32(capi.fptr(x), capi.fptr(dy), capi.fptr(gamma), capi.fptr(mean),
                                                      capi.fptr(rstd), capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc,
                                                      rows_per_dy, float(scale), 0, capi.stream()), "layernorm_bwd")
@@ -800,6 +899,7 @@ class _Sample(torch.autograd.Function):
         capi.check(capi.lib().smml_bilinear_sample_fwd_f32(capi.fptr(x), capi.fptr(vs), capi.fptr(kv), B, Hh, Ww, groups,
                                                            Cc // groups, J, posdim, capi.stream()), "sample_fwd")
         ctx.cfg = (groups, posdim)
+        ctx.det = DETERMINISTIC
         ctx.save_for_backward(x, vs)
         if DECISION_TAP is not None:
             DECISION_TAP.append({"kind": "sample", "vs": vs.detach(), "Hh": Hh, "Ww": Ww, "posdim": posdim})
@@ -811,6 +911,16 @@ class _Sample(torch.autograd.Function):
         groups, posdim = ctx.cfg
         B, Hh, Ww, Cc = x.shape
         J = vs.shape[1]
+        if ctx.det:        # dx is a gather in a fixed order (written in full: no zero fill); dvs has one owner per point either way
+            L = capi.lib()
+            dx = torch.empty_like(x)
+            dvs = _zeros_like(vs)
+            wsb = L.smml_bilinear_sample_bwd_det_workspace_bytes(B, Hh, Ww, groups, J)
+            ws = _scratch(wsb, x.device)
+            capi.check(L.smml_bilinear_sample_bwd_det_f32(capi.fptr(x), capi.fptr(vs), capi.fptr(_c(dkv)), capi.fptr(dx), capi.fptr(dvs),
+                                                          capi.fptr(ws), wsb, B, Hh, Ww, groups, Cc // groups, J, posdim, capi.stream()),
+                       "sample_bwd (deterministic)")
+            return dx, dvs, None, None
         dx = torch.zeros_like(x)
         dvs = _zeros_like(vs)
         capi.check(capi.lib().smml_bilinear_sample_bwd_f32(capi.fptr(x), capi.fptr(vs), capi.fptr(_c(dkv)), capi.fptr(dx),
@@ -1027,6 +1137,9 @@ def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32
             raise ValueError(f"cpb_regions_multi_head=True: the 2-D region path does not support {why}")
         return "region"
     m16 = _dtype16(compute_dtype)
+    if cpb_table and cpb_table != "forward" and DETERMINISTIC:
+        _no_det(f"the table mode of the position bias (cpb_table={cpb_table!r})", "its backward adds d table with float atomics "
+                "(cpb_table_bwd_kernel, dtab)")
     if cpb_table:
         if not log_distance:
             raise NotImplementedError("the table modes are built for the signed-log position transform only")
@@ -1476,7 +1589,7 @@ class _TokenMean(torch.autograd.Function):
     def forward(ctx, x):
         x = _c(x)
         ctx.n = x.shape[1]
-        return colsum(x, 1.0 / x.shape[1])
+        return colsum(x, 1.0 / x.shape[1], det=DETERMINISTIC)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1491,11 +1604,12 @@ def token_mean(x):
 class _TileTokens(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, n):
+        ctx.det = DETERMINISTIC
         return v.unsqueeze(1).repeat(1, n, 1)
 
     @staticmethod
     def backward(ctx, dy):
-        return colsum(_c(dy)), None
+        return colsum(_c(dy), det=ctx.det), None
 
 
 def tile_tokens(v, n: int):
@@ -1515,10 +1629,11 @@ class _Gram(torch.autograd.Function):
     def forward(ctx, x):
         x = _c(x)
         nb, R, K = x.shape
-        g = torch.zeros(nb, R, R, device=x.device, dtype=torch.float32)
+        det = DETERMINISTIC                        # the forward VALUE is a split-K sum; the backward product is not split
+        g = (torch.empty if det else torch.zeros)(nb, R, R, device=x.device, dtype=torch.float32)
         splitk = int(max(1, min((K + 255) // 256, 1024 // max(nb, 1), 65535 // nb)))   # R x R outputs: the K axis is all there is to spread
         _gemm(x, x, g, M=R, N=R, K=K, sam=K, sak=1, sbk=1, sbn=K, ldc=R, nb0=nb, sa0=R * K, sb0=R * K, sc0=R * R,
-              splitk=splitk)
+              splitk=splitk, det=det)
         ctx.save_for_backward(x)
         return g
 
@@ -1616,6 +1731,7 @@ class _MatMul(torch.autograd.Function):
             _gemm(A, B, Cm, M=M, N=N, K=K, sam=sam, sak=sak, sbk=sbk, sbn=sbn, ldc=ldc, residual=Rc, ldr=ldc, nb0=nb0,
                   nb1=nb1, sa0=sa0, sa1=sa1, sb0=sb0, sb1=sb1, sc0=sc0, sc1=sc1, alpha=alpha, beta=beta)
         ctx.cfg = (ta, tb, float(alpha), float(beta), merged, nb0, nb1, M, N, K, R is not None)
+        ctx.det = DETERMINISTIC
         ctx.save_for_backward(A, B)
         return Cm
 
@@ -1636,12 +1752,12 @@ class _MatMul(torch.autograd.Function):
             nb = nb0 * nb1
             splitk = _splitk_for(Mx, Nx, Kx, nb)
             acc = 1 if (bcast or splitk > 1) else 0
-            out = torch.zeros_like(like) if acc else torch.empty_like(like)   # zero-fill only what atomics accumulate into
+            out = torch.zeros_like(like) if (acc and not ctx.det) else torch.empty_like(like)   # zero-fill only what atomics accumulate into
             _gemm(Xa, Xb, out, M=Mx, N=Nx, K=Kx, sam=xa[0], sak=xa[1], sbk=xb[0], sbn=xb[1], ldc=ld_out, nb0=nb0, nb1=nb1,
                   sa0=xa[2], sa1=xa[3], sb0=xb[2], sb1=xb[3],
                   sc0=(out.shape[1] * out.shape[2] * out.shape[3] if out.shape[0] > 1 else 0),
                   sc1=(out.shape[2] * out.shape[3] if out.shape[1] > 1 else 0), alpha=alpha, splitk=splitk,
-                  accumulate=acc)
+                  accumulate=acc, det=ctx.det)
             return out
 
         if ctx.needs_input_grad[0]:
@@ -1771,7 +1887,7 @@ class _SegmentMean(torch.autograd.Function):
         m = n // l
         ctx.l = l
         ctx.shape = x.shape
-        return colsum(x.view(lead * m, l, d), 1.0 / l).view(*x.shape[:-2], m, d)
+        return colsum(x.view(lead * m, l, d), 1.0 / l, det=DETERMINISTIC).view(*x.shape[:-2], m, d)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1796,6 +1912,7 @@ class _ResConv(torch.autograd.Function):
         v = _c(v)
         w2 = _c(w).reshape(w.shape[0], -1)
         B, H, n, D = v.shape
+        ctx.det = DETERMINISTIC
         out = torch.empty(B, n, H * D, device=v.device, dtype=torch.float32)
         capi.check(capi.lib().smml_resconv_fwd_f32(capi.fptr(v), capi.fptr(w2), capi.fptr(out), B, H, n, D, w2.shape[1],
                                                    capi.stream()), "resconv_fwd")
@@ -1806,6 +1923,9 @@ class _ResConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         v, w2 = ctx.saved_tensors
+        if ctx.det:
+            _no_det("resconv backward (res_conv weight gradient)", "the depthwise-convolution weight gradient of the Nystrom block is "
+                    "summed with float atomics (smml_resconv_bwd_f32)")
         B, H, n, D = v.shape
         dv = torch.empty_like(v)
         dw = _zeros_like(w2)
@@ -1825,6 +1945,7 @@ class _DwConv7(torch.autograd.Function):
     def forward(ctx, x, wm, bias):
         x, wm, bias = _c(x), _c(wm), _c(bias)
         B, H, W, Cc = x.shape
+        ctx.det = DETERMINISTIC
         y = torch.empty_like(x)
         capi.check(capi.lib().smml_dwconv7_fwd_f32(capi.fptr(x), capi.fptr(wm), capi.fptr(bias), capi.fptr(y), B, H, W, Cc, 0,
                                                    capi.stream()), "dwconv7_fwd")
@@ -1834,6 +1955,9 @@ class _DwConv7(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, wm = ctx.saved_tensors
+        if ctx.det:
+            _no_det("dwconv7 backward (PPEG weight gradient)", "the depthwise-convolution weight and bias gradients are summed with float "
+                    "atomics (smml_dwconv7_bwd_weight_f32)")
         B, H, W, Cc = x.shape
         dy = _c(dy)
         dx = torch.empty_like(x)
