@@ -243,6 +243,30 @@ int smml_deform_attn_bwd_f32(const float* q, const float* k, const float* v, con
                              float* db3, void* workspace, size_t workspace_bytes, int B, int N, int J, int H,
                              int G, int posdim, float scale, float dropout_p, unsigned long long dropout_seed,
                              void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts);
+/* Wide position-bias family of the fp32-grade core (csrc/deform_attn_wide.hip): the same contract as smml_deform_attn_fwd_f32 / _bwd_f32 for a
+ * bias MLP posdim -> W -> W -> H / G with W = 64 or 128 (dim = 256 / 512 of the modules; W is an argument, anything else is refused).
+ * w1 [W, posdim], b1 [W], w2 [W, W], b2 [W], w3 [H / G, W], b3 [H / G].  The MLP is evaluated once per (bag, group, query, key) in exact
+ * fp32 (layer 2 on v_mfma_f32_32x32x2_f32) into bias tiles of the score layout [B, H, nst / 32, J, 32], which the attention kernel reads:
+ *   training:  pass logits_t (the bias tiles are built there and overwritten in place by the scores) and bias_t = NULL;
+ *   inference: pass logits_t = NULL and bias_t, caller-allocated scratch of the same size.
+ * No ReLU mask is saved: the backward recomputes the MLP with the forward's own evaluator (bit-identical decisions).
+ * smml_deform_attn_wide_decisions (tests) exports those decisions: masks [(B G), N, J, 2, W / 32] uint32 - layer 1 then layer 2, hidden
+ * channel ch at bit ch % 32 of word ch / 32.  Every output is reduced in a fixed order (no float atomics): run-to-run identical.
+ * workspace of the backward: smml_deform_attn_wide_bwd_workspace_bytes, 16-byte aligned (0: unsupported sizes). */
+int smml_deform_attn_wide_fwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                  const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float* out, float* lse,
+                                  float* logits_t, float* bias_t, int B, int N, int J, int H, int G, int W, int posdim, float scale,
+                                  float dropout_p, unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream,
+                                  const SmmlDeformOpts* opts);
+size_t smml_deform_attn_wide_bwd_workspace_bytes(int B, int N, int J, int H, int G, int W);
+int smml_deform_attn_wide_bwd_f32(const float* q, const float* k, const float* v, const float* vs, const float* gq, const float* w1,
+                                  const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const float* out,
+                                  const float* dout, const float* lse, const float* logits_t, float* dlogits_t, float* dq, float* dk, float* dv,
+                                  float* dvs, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* workspace,
+                                  size_t workspace_bytes, int B, int N, int J, int H, int G, int W, int posdim, float scale, float dropout_p,
+                                  unsigned long long dropout_seed, void* ev_start, void* ev_stop, void* stream, const SmmlDeformOpts* opts);
+int smml_deform_attn_wide_decisions(const float* vs, const float* gq, const float* w1, const float* b1, const float* w2, const float* b2,
+                                    unsigned* masks, int B, int N, int J, int G, int W, int posdim, void* stream, const SmmlDeformOpts* opts);
 /* The same fused core with the position bias evaluated EXACTLY PER LINEAR REGION of its MLP (csrc/cpb_regions.h; round 5).  The MLP of
  * models/DeformableAttention2D.py:129-152 is piecewise affine in the signed-log offsets (:148): smml_cpb_regions_build tabulates, for the
  * current parameters, which linear piece every cell of [-pmax, pmax]^2 lies in (cells a ReLU kink crosses carry the kink's line, cells

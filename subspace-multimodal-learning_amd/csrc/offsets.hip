@@ -715,11 +715,16 @@ int smml_bilinear_sample_bwd_f32(const float* x, const float* vs, const float* d
                                  int Hh, int Ww, int G, int cg, int J, int posdim, void* stream) {
   SMML_REQUIRE(x && vs && dkv && dx && dvs, "smml_bilinear_sample_bwd_f32: null pointer");
   SMML_REQUIRE(posdim == 1 || posdim == 2, "smml_bilinear_sample_bwd_f32: posdim must be 1 or 2");
-  SMML_REQUIRE(cg == 16 || cg == 32, "smml_bilinear_sample_bwd_f32: channels per group must be 16 or 32 (got %d)", cg);
+  // cg = 64: one group is one whole wave.  A thread's index is ((b J + j) C + ch) with C = G cg a multiple of 64 and 256-thread blocks, so the
+  // 64 channels of a group start at a multiple of 64 and never straddle a wave; the __shfl_xor ladder of the kernel then starts at 32
+  SMML_REQUIRE(cg == 16 || cg == 32 || cg == 64, "smml_bilinear_sample_bwd_f32: channels per group must be 16, 32 or 64 (got %d)", cg);
   const size_t n = (size_t)B * J * G * cg;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
   if (cg == 16)
     hipLaunchKernelGGL(sample_bwd_kernel<16>, grid, block, 0, (hipStream_t)stream, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J,
+                       posdim);
+  else if (cg == 64)
+    hipLaunchKernelGGL(sample_bwd_kernel<64>, grid, block, 0, (hipStream_t)stream, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J,
                        posdim);
   else
     hipLaunchKernelGGL(sample_bwd_kernel<32>, grid, block, 0, (hipStream_t)stream, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J,
@@ -740,7 +745,7 @@ int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const floa
                                      size_t workspace_bytes, int B, int Hh, int Ww, int G, int cg, int J, int posdim, void* stream) {
   SMML_REQUIRE(x && vs && dkv && dx && dvs && workspace, "smml_bilinear_sample_bwd_det_f32: null pointer");
   SMML_REQUIRE(posdim == 1 || posdim == 2, "smml_bilinear_sample_bwd_det_f32: posdim must be 1 or 2");
-  SMML_REQUIRE(cg == 16 || cg == 32, "smml_bilinear_sample_bwd_det_f32: channels per group must be 16 or 32 (got %d)", cg);
+  SMML_REQUIRE(cg == 16 || cg == 32 || cg == 64, "smml_bilinear_sample_bwd_det_f32: channels per group must be 16, 32 or 64 (got %d)", cg);  // 64: see above
   SMML_REQUIRE(B > 0 && Hh > 0 && Ww > 0 && G > 0 && J > 0, "smml_bilinear_sample_bwd_det_f32: bad size");
   SMML_REQUIRE(J <= SBD_MAXJ, "smml_bilinear_sample_bwd_det_f32: %d keys (the deterministic sampler backward sorts at most %d)", J, SBD_MAXJ);
   SMML_REQUIRE((long long)Hh * Ww <= SBD_MAXPIX, "smml_bilinear_sample_bwd_det_f32: %lld pixels (at most %d)", (long long)Hh * Ww, SBD_MAXPIX);
@@ -757,6 +762,8 @@ int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const floa
   dim3 grid((unsigned)((n + 255) / 256)), gridx((unsigned)((nx + 255) / 256)), block(256);
   if (cg == 16)
     hipLaunchKernelGGL((sample_bwd_kernel<16, false>), grid, block, 0, st, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J, posdim);
+  else if (cg == 64)
+    hipLaunchKernelGGL((sample_bwd_kernel<64, false>), grid, block, 0, st, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J, posdim);
   else
     hipLaunchKernelGGL((sample_bwd_kernel<32, false>), grid, block, 0, st, x, vs, dkv, dx, dvs, B, Hh, Ww, G, J, posdim);
   SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/dvs");
@@ -765,6 +772,8 @@ int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const floa
   SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/sort");
   if (cg == 16)
     hipLaunchKernelGGL(sample_bwd_gather_kernel<16>, gridx, block, 0, st, vs, dkv, keys, start, dx, B, Hh, Ww, G, J, posdim);
+  else if (cg == 64)
+    hipLaunchKernelGGL(sample_bwd_gather_kernel<64>, gridx, block, 0, st, vs, dkv, keys, start, dx, B, Hh, Ww, G, J, posdim);
   else
     hipLaunchKernelGGL(sample_bwd_gather_kernel<32>, gridx, block, 0, st, vs, dkv, keys, start, dx, B, Hh, Ww, G, J, posdim);
   SMML_LAUNCH_CHECK("smml_bilinear_sample_bwd_det_f32/gather");

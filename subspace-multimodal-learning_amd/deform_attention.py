@@ -55,8 +55,8 @@ class CPB(nn.Module):
         for _ in range(depth - 1):
             self.mlp.append(nn.Sequential(nn.Linear(dim, dim), nn.ReLU()))
         self.mlp.append(nn.Linear(dim, heads // offset_groups))
-        if depth != 2 or dim != 32:
-            raise NotImplementedError("the position-bias kernels are built for depth 2 and width 32 (dim = 128)")
+        if depth != 2 or dim not in (32, 64, 128):
+            raise NotImplementedError("the position-bias kernels are built for depth 2 and width 32, 64 or 128 (dim = 128, 256 or 512)")
 
     def tensors(self):
         m = self.mlp
@@ -166,6 +166,8 @@ class DeformCrossAttention2D(nn.Module):
     def _regions_apply(self, n_tokens: int) -> bool:
         """Whether forward_tokens on a bag of n_tokens takes the region path with the pmax of _region_pmax (functional.deform_path)."""
         if self.consistent_grid_norm or not self.rel_pos_bias.mlp[0][0].weight.is_cuda:
+            return False
+        if tuple(self.rel_pos_bias.mlp[1][0].weight.shape) != (32, 32):      # widths 64 / 128 (dim = 256 / 512): no region path
             return False
         Hh, Ww = self._grid(n_tokens)
         L = Fh.capi.lib()

@@ -1112,17 +1112,46 @@ def region1d_unsupported(vs, k, w2, w3, *, heads: int, groups: int, compute_dtyp
     return _region_why(1, k.shape[1], w2.shape, w3.shape, heads, groups, compute_dtype, cpb_table, True, log_distance, True, False)
 
 
+WIDE_W2_SHAPES = ((64, 64), (128, 128))      # layer 2 of the bias MLP at dim = 256 / 512: the wide family (csrc/deform_attn_wide.hip)
+
+
+def _wide_path(posdim, heads, groups, w2_shape, w3_shape, log_distance, compute_dtype, cpb_table, cpb_regions, regions_multi_head) -> str:
+    """'pair_wide', or ValueError naming the option the wide family (bias-MLP width 64 / 128) does not have: it is the fp32-grade per-pair
+    core alone."""
+    W = int(w2_shape[0])
+    what = f"a position-bias MLP of width {W} (dim = {4 * W})"
+    if _dtype16(compute_dtype) is not None:
+        raise ValueError(f"compute_dtype={compute_dtype!r}: the 16-bit compute modes are built for width 32 (dim = 128), not for {what}")
+    if cpb_table:
+        raise ValueError(f"cpb_table={cpb_table!r}: the table modes are built for width 32 (dim = 128), not for {what}")
+    if regions_multi_head:
+        raise ValueError(f"cpb_regions_multi_head=True: the 2-D region path is built for width 32 (dim = 128), not for {what}")
+    if cpb_regions is not None and bool(cpb_regions):
+        name = "cpb_regions=True (the 1-D piece path, cpb_regions_1d)" if posdim == 1 else "cpb_regions=True (the region path)"
+        raise ValueError(f"{name} is built for width 32 (dim = 128), not for {what}")
+    if not log_distance and posdim != 1:
+        raise NotImplementedError("the raw-offset position transform (cpb_log_distance=False) exists for 1-D positions without the table modes")
+    hpg = heads // groups if groups > 0 and heads % groups == 0 else 0
+    if hpg not in (1, 2) or tuple(w3_shape) != (hpg, W):
+        raise ValueError(f"{what} needs heads // groups in (1, 2) and w3 of shape (heads // groups, {W}); got heads {heads}, groups {groups}, "
+                         f"w3 {tuple(w3_shape)}")
+    return "pair_wide"
+
+
 def deform_path(*, posdim: int, heads: int, groups: int, keys: int, w2_shape=(32, 32), w3_shape=(1, 32), log_distance: bool = True,
                 compute_dtype=None, cpb_table=False, cpb_regions=None, region_pmax_given: bool = False, capturing: bool = False,
                 regions_multi_head: bool = False) -> str:
     """The core a deform_attention call with these shapes and options takes: 'region1d' (the 1-D position bias per linear piece), 'table',
-    'pair_table_forward' (per-pair backward of a table forward), 'region' (2-D, per linear region; fp32-grade or 16-bit core) or 'pair'
-    (the per-pair MLP; fp32-grade or 16-bit core).  Raises on a combination no core supports.  No GPU work; the module switches
+    'pair_table_forward' (per-pair backward of a table forward), 'region' (2-D, per linear region; fp32-grade or 16-bit core), 'pair'
+    (the per-pair MLP; fp32-grade or 16-bit core) or 'pair_wide' (bias-MLP width 64 / 128, w2_shape (64, 64) / (128, 128): the per-pair MLP in
+    exact fp32, fp32-grade core only - every region, table or 16-bit option raises ValueError there).  Raises on a combination no core supports.  No GPU work; the module switches
     (CPB_REGIONS) are read at call time.  capturing: the call is being captured in a hipGraph (a 2-D region call then needs its pmax).
     regions_multi_head (2-D positions): the region path on request for one or two heads per offset group, in either compute mode; any
     combination it does not support raises ValueError (never a silent fall-back).  Without it the rules above are unchanged."""
     if cpb_table not in (False, True, None, "forward", "full"):
         raise ValueError("cpb_table must be False, True / 'full' or 'forward'")
+    if tuple(w2_shape) in WIDE_W2_SHAPES:
+        return _wide_path(posdim, heads, groups, w2_shape, w3_shape, log_distance, compute_dtype, cpb_table, cpb_regions, regions_multi_head)
     if cpb_regions is not None and bool(cpb_regions) and posdim == 1:
         # 1-D positions: the piece path only on request (cpb_regions=True), and never a silent fall-back from it
         why = _region_why(1, keys, w2_shape, w3_shape, heads, groups, compute_dtype, cpb_table, True, log_distance, True, False)
@@ -1411,6 +1440,77 @@ class _DeformAttnPair(torch.autograd.Function):
         return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
 
+def wide_decisions(vs, gq, w1, b1, w2, b2, *, B: int, N: int, J: int, groups: int, log_distance: bool = True):
+    """Tests: the ReLU decisions of the wide position-bias MLP (width 64 / 128) exactly as its forward and backward take them
+    (smml_deform_attn_wide_decisions) -> (m1, m2) bool [(B groups), N, J, W]: [x1 > 0], [x2 > 0] per pair and hidden channel."""
+    W = w2.shape[0]
+    words = torch.empty(B * groups, N, J, 2, W // 32, device=vs.device, dtype=torch.int32)
+    capi.check(capi.lib().smml_deform_attn_wide_decisions(*(capi.fptr(_c(t.detach())) for t in (vs, gq, w1, b1, w2, b2)), capi.ptr(words), B, N, J,
+                                                          groups, W, vs.shape[-1], capi.stream(), capi.deform_opts(None, log_distance)),
+               "deform_attn_wide_decisions")
+    bits = ((words[..., None] >> torch.arange(32, device=vs.device, dtype=torch.int32)) & 1).bool()      # [..., 2, W / 32, 32]
+    bits = bits.reshape(B * groups, N, J, 2, W)
+    return bits[..., 0, :], bits[..., 1, :]
+
+
+class _DeformAttnWide(torch.autograd.Function):
+    """The fp32-grade fused core for a bias MLP of width 64 / 128 (csrc/deform_attn_wide.hip): the forward evaluates the MLP once per pair
+    into bias tiles and runs the attention kernel on them, the backward is the dq / dkv passes of the width-32 core followed by the wide
+    bias backward, which recomputes the MLP - no ReLU mask is saved.  No host synchronisation and no float atomics: the call captures in a
+    hipGraph as it stands and is run-to-run identical with or without functional.deterministic()."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, log_distance):
+        ctx.fork = fork
+        ctx.seed_offset = seed_offset
+        ctx.log_distance = bool(log_distance)
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
+        B, N, _ = q.shape
+        J = k.shape[1]
+        posdim = vs.shape[-1]
+        W = w2.shape[0]
+        _check_core(q, heads)
+        if tuple(w1.shape) != (W, posdim) or tuple(w3.shape) != (heads // groups, W) or tuple(b1.shape) != (W,) or tuple(b2.shape) != (W,):
+            raise RuntimeError(f"the wide position-bias MLP is {posdim} -> {W} -> {W} -> heads // groups; got w1 {tuple(w1.shape)}, "
+                               f"w3 {tuple(w3.shape)}")
+        L = capi.lib()
+        out, lse = _out_lse(q, heads)
+        # training: the bias tiles are built in logits_t and overwritten in place by the scores; inference: a scratch buffer of that size
+        logits = _score_tiles(q, heads, J, torch.float32) if any(ctx.needs_input_grad) else None
+        bias = _score_tiles(q, heads, J, torch.float32) if logits is None else None
+        capi.check(L.smml_deform_attn_wide_fwd_f32(
+            *(capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse)), capi.fptr(logits), capi.fptr(bias), B, N, J, heads,
+            groups, W, posdim, float(scale), float(dropout_p), int(dropout_seed), *TIMER.events("deform_wide_fwd", B * heads * N * J),
+            capi.stream(), capi.deform_opts(seed_offset, ctx.log_distance)), "deform_attn_wide_fwd")
+        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed))
+        ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits)
+        if DECISION_TAP is not None:
+            m1, m2 = wide_decisions(vs, gq, w1, b1, w2, b2, B=B, N=N, J=J, groups=groups, log_distance=ctx.log_distance)
+            DECISION_TAP.append({"kind": "attn", "wide": W, "masks1": m1, "masks2": m2, "vs": vs.detach(), "gq": gq.detach(), "B": B, "N": N,
+                                 "J": J, "heads": heads, "groups": groups, "log_distance": ctx.log_distance})
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits = ctx.saved_tensors
+        heads, groups, scale, dropout_p, dropout_seed = ctx.cfg
+        B, N, _ = q.shape
+        J = k.shape[1]
+        W = w2.shape[0]
+        L = capi.lib()
+        dout = _c(dout)
+        dlogits = _dscores(logits, None)
+        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
+        wsb = L.smml_deform_attn_wide_bwd_workspace_bytes(B, N, J, heads, groups, W)
+        ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
+        capi.check(L.smml_deform_attn_wide_bwd_f32(
+            *(capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, dout, lse, logits, dlogits, dq, dk, dv, dvs, dw1, db1, dw2,
+                                     db2, dw3, db3)), capi.fptr(ws), wsb, B, N, J, heads, groups, W, vs.shape[-1], scale, dropout_p, dropout_seed,
+            *TIMER.events("cpb_wide_bwd", B * heads * N * J), capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance)),
+            "deform_attn_wide_bwd")
+        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
+
+
 # ------------------------------------------------------------------------------------------------
 # table mode of the 16-bit core: the position-bias MLP evaluated once per call on a grid, interpolated per pair (include/smml.h)
 # ------------------------------------------------------------------------------------------------
@@ -1546,13 +1646,19 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
     fp32-grade core, heads // groups in {1, 2}; anything else raises), cpb_region_pmax = half-width of its index grid (None: the span of
     the breakpoints; no host sync either way).
     cpb_regions_multi_head True with 2-D positions: the position bias per linear region also for two heads per offset group (w3 [2, 32];
-    include/smml.h "_mh" entry points; signed-log offsets, either compute mode, no table mode; anything else raises)."""
+    include/smml.h "_mh" entry points; signed-log offsets, either compute mode, no table mode; anything else raises).
+    w2 of shape (64, 64) / (128, 128) (dim = 256 / 512 of the modules): the wide family (csrc/deform_attn_wide.hip) - the per-pair MLP in exact
+    fp32, fp32-grade core, one or two heads per group, all three position forms; compute_dtype, cpb_table, cpb_regions and
+    cpb_regions_multi_head raise ValueError there."""
     mh = bool(cpb_regions_multi_head) and vs.shape[-1] == 2
     path = deform_path(posdim=vs.shape[-1], heads=heads, groups=groups, keys=k.shape[1], w2_shape=w2.shape, w3_shape=w3.shape,
                        log_distance=log_distance, compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions,
                        region_pmax_given=cpb_region_pmax is not None,
                        capturing=cpb_region_pmax is None and q.is_cuda and torch.cuda.is_current_stream_capturing(),
                        regions_multi_head=mh)
+    if path == "pair_wide":       # width 64 / 128: the region tables, their prefetch and pmax are not consulted
+        return _DeformAttnWide.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
+                                     dropout_seed_offset, fork, log_distance)
     if path in ("region", "region1d"):
         pmax = cpb_region_pmax
         if path == "region" and pmax is None:      # from the data: one host sync
