@@ -452,6 +452,25 @@ int smml_deform_attn_dropout_mask_f32(float* mask, int B, int N, int J, int H, f
 int smml_deform_attn_relu1_masks(const float* vs, const float* gq, const float* w1, const float* b1, unsigned short* masks,
                                  int B, int N, int J, int G, int posdim, void* stream, const SmmlDeformOpts* opts);
 
+/* Attention maps (csrc/attn_maps.hip): where a fused deformable cross-attention call looked, from what its forward saved.  Input: the score
+ * tiles logits_t [B, H, nst / 32, J, 32] fp32 and lse [B, H, N] of ANY fp32-grade forward above (pair, wide in its training form, region,
+ * region_mh, region1d; not the fp16 tiles of the 16-bit cores).  The probabilities P[b, h, i, j] = exp(logits - lse) (natural base) are the
+ * softmax BEFORE dropout (DeformableAttention2D.py:306-308, 1D :226-228); nothing of the forward is recomputed.
+ *   key_mass [B, H, J] = (1 / N) sum_i P[b, h, i, j], always written; every row sums to 1
+ *   attn     [B, H, N, J] = P, nullable (B H N J floats: small bags and tests)
+ * One pass over logits_t (16 bytes per lane); the padding rows N .. nst - 1 of the last tiles never enter a sum.  The column sums go through
+ * partial rows [B, H, ceil(ceil(N / 32) / 8), J] in `workspace` (smml_attn_maps_workspace_bytes bytes, 16-byte aligned; 0 for a non-positive
+ * size; logits_t 16-byte aligned too) that a second kernel adds in ascending order: no float atomics, run-to-run identical. */
+size_t smml_attn_maps_workspace_bytes(int B, int N, int J, int H);
+int smml_attn_maps_f32(const float* logits_t, const float* lse, float* key_mass, float* attn, void* workspace, size_t workspace_bytes,
+                       int B, int N, int J, int H, void* stream);
+/* The mass on the patch grid (csrc/offsets.hip): per (bag, offset group) the mean of key_mass over the group's H / G heads, distributed to
+ * the Hh x Ww map the keys were sampled from with the four corner weights and in-bounds masks of smml_bilinear_sample_fwd_f32 (the same
+ * integer path: the adjoint of that gather).  Mass at corners outside the map is dropped as the sampler drops their features, so a map sums
+ * to at most 1.  2-D positions only: vs [(B G), J, 2]; patch_map [B, G, Hh, Ww] is overwritten.  Additions in a fixed (key, corner) order per
+ * pixel: no atomics, run-to-run identical.  Ww <= 8192. */
+int smml_attn_splat_f32(const float* key_mass, const float* vs, float* patch_map, int B, int H, int G, int J, int Hh, int Ww, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Nystrom landmark self-attention, HBM-bound pieces (the contractions of models/NystromAttention.py:86,
  * 122-140 and the pinv iteration :20-35 run through smml_gemm_f32 with alpha / beta epilogues).

@@ -77,6 +77,9 @@ SIGNATURES = {
     "smml_deform_attn_fwd_f32": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
     "smml_deform_attn_dropout_mask_f32": (_i, [_f, _i, _i, _i, _i, _fl, C.c_ulonglong, _f] + [_o]),
     "smml_deform_attn_relu1_masks": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f] + [_o]),
+    "smml_attn_maps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smml_attn_maps_f32": (_i, [_f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _f]),
+    "smml_attn_splat_f32": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _f]),
     "smml_deform_attn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "smml_deform_attn_bwd_f32": (_i, [_f] * 27 + [_f, _sz, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
     "smml_deform_attn_wide_fwd_f32": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),

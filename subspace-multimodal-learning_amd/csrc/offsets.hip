@@ -571,6 +571,74 @@ __global__ void corners_kernel(const float* __restrict__ vs, int* __restrict__ c
   cm[4 * i + 2] = k.mx0 && k.my1; cm[4 * i + 3] = k.mx1 && k.my1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// attention splat: the adjoint of the bilinear gather applied to the attention mass of the sampled keys.  Per (bag, group) the mean over
+// the group's heads of key_mass [B, H, J] is distributed to the Hh x Ww patch grid with the four corner weights and in-bounds masks
+// sample_fwd_kernel applies (corners_of: the same integer path, bit for bit); mass at corners outside the map is dropped as the sampler
+// drops their features.  A workgroup keeps SPLAT_PIX pixels (whole rows) of one (bag, group) in LDS and walks ALL keys in chunks: the
+// chunk's 4 SPLAT_CHUNK (pixel, value) contributions are staged in key-major, corner-minor order, then every thread scans them and adds
+// those of the pixels it owns (pixel % threads) - each pixel receives its contributions in ascending (key, corner) order whatever the
+// tiling: a fixed order of additions, no atomics.
+// ---------------------------------------------------------------------------------------------
+constexpr int SPLAT_THREADS = 256, SPLAT_CHUNK = 256, SPLAT_PIX = 8192;
+static_assert(SPLAT_THREADS == SPLAT_CHUNK && SPLAT_CHUNK % 4 == 0, "a thread stages one key of a chunk; the scan reads groups of four keys");
+__global__ __launch_bounds__(SPLAT_THREADS) void attn_splat_kernel(const float* __restrict__ mass, const float* __restrict__ vs,
+                                                                   float* __restrict__ pmap, int H, int G, int J, int Hh, int Ww,
+                                                                   int rows_per_tile) {
+  __shared__ float img[SPLAT_PIX];
+  __shared__ __attribute__((aligned(16))) int spix[4 * SPLAT_CHUNK];
+  __shared__ __attribute__((aligned(16))) float sval[4 * SPLAT_CHUNK];
+  const int tid = threadIdx.x;
+  const int bg = blockIdx.x, b = bg / G, g = bg - b * G, o = H / G;
+  const int y_lo = blockIdx.y * rows_per_tile, y_hi = min(y_lo + rows_per_tile, Hh);
+  const int npix = (y_hi - y_lo) * Ww;
+  for (int p = tid; p < npix; p += SPLAT_THREADS) img[p] = 0.f;
+  const float* mp = mass + ((size_t)b * H + (size_t)g * o) * J;
+  const float* vp = vs + (size_t)bg * J * 2;
+  for (int j0 = 0; j0 < J; j0 += SPLAT_CHUNK) {
+    const int nk = min(SPLAT_CHUNK, J - j0);
+    __syncthreads();                                   // the image is zeroed / the previous chunk's scan is over
+    if (tid < nk) {
+      const int j = j0 + tid;
+      float m = 0.f;
+      for (int oi = 0; oi < o; ++oi) m += mp[(size_t)oi * J + j];
+      m = m / (float)o;
+      const Corners k = corners_of(vp[(size_t)j * 2], vp[(size_t)j * 2 + 1], Ww, Hh);
+      const float wx1 = k.fx, wx0 = 1.f - k.fx, wy1 = k.fy, wy0 = 1.f - k.fy;
+      const bool r0 = k.my0 && k.y0 >= y_lo && k.y0 < y_hi, r1 = k.my1 && (k.y0 + 1) >= y_lo && (k.y0 + 1) < y_hi;
+      // pixel of corner (x0, y0) in this tile's image; a far-away point (no corner in the map) takes 0: no index is formed from it
+      const int p00 = ((k.mx0 || k.mx1) && (k.my0 || k.my1)) ? (k.y0 - y_lo) * Ww + k.x0 : 0;
+      spix[4 * tid + 0] = (r0 && k.mx0) ? p00 : -1;
+      spix[4 * tid + 1] = (r0 && k.mx1) ? p00 + 1 : -1;
+      spix[4 * tid + 2] = (r1 && k.mx0) ? p00 + Ww : -1;
+      spix[4 * tid + 3] = (r1 && k.mx1) ? p00 + Ww + 1 : -1;
+      sval[4 * tid + 0] = m * (wx0 * wy0);
+      sval[4 * tid + 1] = m * (wx1 * wy0);
+      sval[4 * tid + 2] = m * (wx0 * wy1);
+      sval[4 * tid + 3] = m * (wx1 * wy1);
+    } else {
+      *reinterpret_cast<int4*>(&spix[4 * tid]) = make_int4(-1, -1, -1, -1);      // past the last key: the scan below reads whole groups
+    }
+    __syncthreads();
+    // four keys (16 contributions) per step: the four 16-byte reads are in flight together, the adds stay in (key, corner) order
+    for (int k0 = 0; k0 < nk; k0 += 4) {
+      int4 pk[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pk[i] = *reinterpret_cast<const int4*>(&spix[4 * (k0 + i)]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int pc[4] = {pk[i].x, pk[i].y, pk[i].z, pk[i].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (pc[c] >= 0 && (pc[c] & (SPLAT_THREADS - 1)) == tid) img[pc[c]] += sval[4 * (k0 + i) + c];
+      }
+    }
+  }
+  __syncthreads();
+  float* out = pmap + ((size_t)bg * Hh + y_lo) * Ww;
+  for (int p = tid; p < npix; p += SPLAT_THREADS) out[p] = img[p];
+}
+
 }  // namespace
 
 extern "C" {
@@ -787,6 +855,24 @@ int smml_bilinear_corners_f32(const float* vs, int* cx, int* cy, unsigned char* 
   hipLaunchKernelGGL(corners_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, vs, cx, cy, cm, n, Hh, Ww,
                      posdim);
   SMML_LAUNCH_CHECK("smml_bilinear_corners_f32");
+  return SMML_OK;
+}
+
+// patch_map [B, G, Hh, Ww] OVERWRITTEN: the mean over each group's heads of key_mass [B, H, J], splatted to the patch grid at vs [(B G), J, 2]
+// with the sampler's corner weights and masks (2-D positions).  Fixed order of additions: run-to-run identical.
+int smml_attn_splat_f32(const float* key_mass, const float* vs, float* patch_map, int B, int H, int G, int J, int Hh, int Ww, void* stream) {
+  const char* fn = "smml_attn_splat_f32";
+  SMML_REQUIRE(B > 0 && H > 0 && G > 0 && J > 0 && Hh > 0 && Ww > 0, "%s: bad size", fn);
+  SMML_REQUIRE(H % G == 0, "%s: heads (%d) must be divisible by offset groups (%d)", fn, H, G);
+  SMML_REQUIRE(key_mass && vs && patch_map, "%s: null pointer", fn);
+  SMML_REQUIRE(Ww <= SPLAT_PIX, "%s: %d columns (a workgroup keeps whole rows of at most %d pixels in LDS)", fn, Ww, SPLAT_PIX);
+  SMML_REQUIRE((long long)B * G <= 2147483647LL && (long long)B * H <= 2147483647LL, "%s: too many (bag, group) pairs", fn);
+  const int rows = SPLAT_PIX / Ww;
+  const int tiles = (Hh + rows - 1) / rows;
+  SMML_REQUIRE(tiles <= 65535, "%s: %d rows of %d columns need %d row tiles (at most 65535)", fn, Hh, Ww, tiles);
+  hipLaunchKernelGGL(attn_splat_kernel, dim3((unsigned)(B * G), (unsigned)tiles), dim3(SPLAT_THREADS), 0, (hipStream_t)stream, key_mass, vs,
+                     patch_map, H, G, J, Hh, Ww, rows);
+  SMML_LAUNCH_CHECK("smml_attn_splat_f32");
   return SMML_OK;
 }
 

@@ -20,9 +20,14 @@ Corrected-semantics switches, OFF by default (bit-parity w
   * DeformCrossAttention1D(true_1d_sampling=True): the reference's grid_sample_1d (:36-43) lays the features out
     [H = n, W = 1] while the grid carries (x = vs, y = 0), so every "sampled" key is the centre token scaled; with the switch
     the map is [H = 1, W = n] and vs interpolates along the tokens.
+Attention maps (additive; default off): `forward_tokens(..., return_attn_maps=True)` / `forward(..., return_attn_maps=True)` append a dict
+{"key_mass" [B, heads, J], "patch_map" [B, groups, rows, cols] (2-D module only), "vs", "vgrid"} to the return value - the pre-dropout
+softmax of the SAME fused forward launch, reduced by functional.deform_attention_maps; "dense" adds "attn" [B, heads, N, J].  The fp32-grade
+cores only (compute_dtype / cpb_table raise ValueError).
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -79,6 +84,31 @@ def _dropout_args(mod, device=None):
 
 _GRID_CACHE = {}
 _GRAD_FORK = __import__("os").environ.get("SMML_GRAD_FORK", "1") != "0"       # measurement switch (functional.GradFork)
+
+
+def _maps_arg(mod, return_attn_maps):
+    """return_attn_maps of a module's forward -> (an AttnScores sink or None, dense); the modes without maps are refused before any launch"""
+    if return_attn_maps not in (False, True, None, "dense"):
+        raise ValueError("return_attn_maps must be False, True or 'dense'")
+    if not return_attn_maps:
+        return None, False
+    if mod.cpb_table:
+        raise ValueError(f"cpb_table={mod.cpb_table!r}: attention maps are built for the fp32-grade cores, not for the table modes")
+    if mod.compute_dtype is not None:
+        raise ValueError(f"compute_dtype={mod.compute_dtype!r}: attention maps are built for the fp32-grade cores, not for the 16-bit compute modes")
+    return Fh.AttnScores(), return_attn_maps == "dense"
+
+
+def _with_attn_maps(forward):
+    """The channels-first forward of the reference plus the additive keyword-only return_attn_maps.  The reference's forward is kept as
+    written and stays what inspect.signature reports (functools.wraps): (x1, x2, return_vgrid=False)."""
+    @functools.wraps(forward)
+    def with_maps(self, x1, x2, return_vgrid=False, *, return_attn_maps=False):
+        if not return_attn_maps:
+            return forward(self, x1, x2, return_vgrid)
+        r = self.forward_tokens(x1.transpose(1, 2), x2.transpose(1, 2), return_vgrid, return_attn_maps=return_attn_maps)
+        return (r[0].transpose(1, 2),) + tuple(r[1:])
+    return with_maps
 
 
 def _grid_queries_2d(Hh: int, Ww: int, device) -> torch.Tensor:
@@ -187,8 +217,11 @@ class DeformCrossAttention2D(nn.Module):
         Hh, Ww = self._grid(n_tokens)
         self._prefetch = Fh.RegionPrefetch(*self.rel_pos_bias.tensors(), self._region_pmax(Hh, Ww))
 
-    def forward_tokens(self, x1t, x2t, return_vgrid=False, residual=None):
-        """Token-major entry: x1t (queries) / x2t (keys, values) [B, N, C] -> [B, N, C] (+ residual)."""
+    def forward_tokens(self, x1t, x2t, return_vgrid=False, residual=None, return_attn_maps=False):
+        """Token-major entry: x1t (queries) / x2t (keys, values) [B, N, C] -> [B, N, C] (+ residual).  return_attn_maps (True | 'dense'): the
+        attention maps of this call (module docstring) are appended to the return value; patch_map lies on the grid and at the sample
+        positions the module sampled with, whichever normalisation is on."""
+        sink, dense = _maps_arg(self, return_attn_maps)
         B, N, C = x1t.shape
         Hh, Ww = self._grid(N)
         G, H = self.offset_groups, self.heads
@@ -224,13 +257,20 @@ class DeformCrossAttention2D(nn.Module):
         if self.cpb_regions_multi_head:
             tab["cpb_regions_multi_head"] = True
         o = Fh.deform_attention(q, k, v, vs, gq, *self.rel_pos_bias.tensors(), heads=H, groups=G, scale=self.scale,
-                                compute_dtype=self.compute_dtype, fork=fork, **tab, **_dropout_args(self, q.device))
+                                compute_dtype=self.compute_dtype, fork=fork, **tab, **_dropout_args(self, q.device),
+                                **({} if sink is None else {"attn_scores": sink}))
         # the output projection follows the core's compute mode (single-term 16-bit operands, fp32 accumulation and storage)
         out = Fh.linear(o, self.to_out.weight.reshape(self.dim, -1), self.to_out.bias, residual=residual, prec=Fh.prec16(self.compute_dtype))
-        return (out, vgrid) if return_vgrid else out
+        ret = (out, vgrid) if return_vgrid else (out,)
+        if sink is not None:
+            maps = Fh.deform_attention_maps(sink, vs, heads=H, groups=G, grid_hw=(Hh, Ww), dense=dense)
+            ret += ({**maps, "vs": vs.detach(), "vgrid": vgrid.detach()},)
+        return ret if len(ret) > 1 else out
 
+    @_with_attn_maps
     def forward(self, x1, x2, return_vgrid=False):
-        """x1, x2 [B, C, N] channels-first as in the reference -> [B, C, N] (and vgrid [(B g), 2, th, tw])."""
+        """x1, x2 [B, C, N] channels-first as in the reference -> [B, C, N] (and vgrid [(B g), 2, th, tw]).  Keyword-only
+        return_attn_maps (True | 'dense'): the attention maps of the call are appended (module docstring)."""
         r = self.forward_tokens(x1.transpose(1, 2), x2.transpose(1, 2), return_vgrid)
         if return_vgrid:
             return r[0].transpose(1, 2), r[1]
@@ -288,7 +328,10 @@ class DeformCrossAttention1D(nn.Module):
         self.to_v = nn.Conv1d(dim, inner_dim, 1, groups=offset_groups if group_key_values else 1, bias=False)
         self.to_out = nn.Conv1d(inner_dim, dim, 1)
 
-    def forward_tokens(self, x1t, x2t, return_vgrid=False, residual=None):
+    def forward_tokens(self, x1t, x2t, return_vgrid=False, residual=None, return_attn_maps=False):
+        """return_attn_maps (True | 'dense'): the attention maps of this call are appended to the return value - without a patch map: the
+        default sampler reads the centre token for every key (the bug-compatible degenerate axis), so a splat says nothing there."""
+        sink, dense = _maps_arg(self, return_attn_maps)
         B, n, C = x1t.shape
         G, H = self.offset_groups, self.heads
         q = Fh.grouped_pointwise(x1t, self.to_q.weight, G if self.group_queries else 1)
@@ -311,10 +354,15 @@ class DeformCrossAttention1D(nn.Module):
             tab = {"cpb_regions": True, "cpb_region_pmax": Fh.table_pmax(1.0, 1.0 + 2.0 * self.offset_scale / max(t - 1, 1))}
         o = Fh.deform_attention(q, k, v, vs, seq.contiguous(), *self.rel_pos_bias.tensors(), heads=H, groups=G,
                                 scale=self.scale, compute_dtype=self.compute_dtype, log_distance=self.cpb_log_distance, **tab,
-                                **_dropout_args(self, q.device))
+                                **_dropout_args(self, q.device), **({} if sink is None else {"attn_scores": sink}))
         out = Fh.linear(o, self.to_out.weight.reshape(self.dim, -1), self.to_out.bias, residual=residual, prec=Fh.prec16(self.compute_dtype))
-        return (out, vgrid) if return_vgrid else out
+        ret = (out, vgrid) if return_vgrid else (out,)
+        if sink is not None:
+            maps = Fh.deform_attention_maps(sink, heads=H, groups=G, dense=dense)
+            ret += ({**maps, "vs": vs.detach(), "vgrid": vgrid.detach()},)
+        return ret if len(ret) > 1 else out
 
+    @_with_attn_maps
     def forward(self, x1, x2, return_vgrid=False):
         r = self.forward_tokens(x1.transpose(1, 2), x2.transpose(1, 2), return_vgrid)
         if return_vgrid:

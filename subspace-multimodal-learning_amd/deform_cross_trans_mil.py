@@ -51,14 +51,14 @@ class DeformCrossTransLayer(nn.Module):
         self.attn1d = DeformCrossAttention1D(dim=128, downsample_factor=4, offset_scale=2, offset_kernel_size=6,
                                              compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions_1d)
 
-    def forward(self, x1, x2, attn_dim, return_vgrid):
+    def forward(self, x1, x2, attn_dim, return_vgrid, return_attn_maps=False):
         n = self.norm
         a = Fh.layer_norm(x1, n.weight, n.bias, n.eps)
         b = Fh.layer_norm(x2, n.weight, n.bias, n.eps)
         if attn_dim == 1:
-            return self.attn1d.forward_tokens(a, b, False, residual=x1)
+            return self.attn1d.forward_tokens(a, b, False, residual=x1, return_attn_maps=return_attn_maps)
         if attn_dim == 2:
-            return self.attn2d.forward_tokens(a, b, bool(return_vgrid), residual=x1)
+            return self.attn2d.forward_tokens(a, b, bool(return_vgrid), residual=x1, return_attn_maps=return_attn_maps)
         raise ValueError(f"attn_dim must be 1 or 2 (got {attn_dim})")
 
 
@@ -95,6 +95,7 @@ class DeformCrossTransMIL(nn.Module):
         self._fc2 = nn.Linear(args.path_dim, self.n_classes)
         self.pooler = Pooler(args.path_dim)
         self.multimodal_projection = nn.Linear(args.path_dim, self.args.path_dim)
+        self._maps_out = None         # attention_maps(): a list that the 2-D branch's forward appends its maps to; None otherwise
 
     def prefetch(self, n_tokens: int) -> None:
         """Work that depends on the parameters only and can run beside the first layers: the position bias's region tables."""
@@ -128,7 +129,11 @@ class DeformCrossTransMIL(nn.Module):
                 add = side * side - N
                 h = torch.cat((h, h[:, :add]), dim=1)
                 pth = torch.cat((path, path[:, :add]), dim=1)
-            if self.args.return_vgrid:
+            if self._maps_out is not None:            # attention_maps(): the same forward, the attention's maps kept
+                r = self.layer3(h, pth, 2, bool(self.args.return_vgrid), return_attn_maps=self._maps_out[0])
+                h, vgrid = r[0], (r[1] if self.args.return_vgrid else None)
+                self._maps_out.append(r[-1])
+            elif self.args.return_vgrid:
                 h, vgrid = self.layer3(h, pth, 2, True)
             else:
                 h = self.layer3(h, pth, 2, False)
@@ -148,3 +153,21 @@ class DeformCrossTransMIL(nn.Module):
             omic_tiled = Fh.tile_tokens(omic, N)                 # omic.unsqueeze(1).repeat(1, N, 1), :104
             return encoded, logits, path_grads, omic_tiled, vgrid
         return encoded, logits, path_grads
+
+    def _maps_check(self):
+        if self.args.attn_dim != 2:
+            raise ValueError(f"attention_maps needs attn_dim = 2 (got {self.args.attn_dim}): the 1-D branch's default sampler reads the centre "
+                             "token for every key, so its attention says nothing about where in the bag the model looked")
+
+    def attention_maps(self, path, omic, dense: bool = False):
+        """The normal forward, once, under no_grad -> (its outputs, maps): maps = the dict of DeformCrossAttention2D's return_attn_maps
+        ("key_mass" [B, heads, J], "patch_map" [B, groups, rows, cols], "vs", "vgrid"; dense: + "attn") of the one attention call.  With
+        wrap_pad_to_square the maps lie on the padded grid.  attn_dim = 2 only."""
+        self._maps_check()
+        self._maps_out = ["dense" if dense else True]
+        try:
+            with torch.no_grad():
+                out = self.forward(path, omic)
+            return out, self._maps_out[1]
+        finally:
+            self._maps_out = None

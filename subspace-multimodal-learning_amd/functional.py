@@ -1208,6 +1208,21 @@ def _score_tiles(q, heads: int, J: int, dtype, *inner):
     return torch.empty(B, heads, nst // 32, J, *inner, 32, device=q.device, dtype=dtype)
 
 
+class AttnScores:
+    """Sink for what ONE deform_attention call saved of its softmax (deform_attention(..., attn_scores=AttnScores())): the score tiles
+    logits_t [B, H, nst / 32, J, 32] fp32 and lse [B, H, N] of include/smml.h, kept whether or not a backward follows - the fused forward
+    writes them in the same launch that computes `out`.  deform_attention_maps turns them into maps.  Detached; the fp32-grade cores only."""
+
+    def __init__(self):
+        self.logits = self.lse = None
+        self.heads = self.groups = None
+
+
+def _keep_scores(scores, logits, lse, heads: int, groups: int) -> None:
+    if scores is not None:
+        scores.logits, scores.lse, scores.heads, scores.groups = logits.detach(), lse.detach(), int(heads), int(groups)
+
+
 def _dscores(logits, m16):
     """The d scores of a backward: the scores' shape, fp32 (fp32-grade core) or bf16 (16-bit core)."""
     return torch.empty(logits.shape, device=logits.device, dtype=torch.float32 if m16 is None else torch.bfloat16)
@@ -1255,7 +1270,7 @@ class _DeformAttnRegion(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
-                pmax, prefetch, multi_head=False):
+                pmax, prefetch, multi_head=False, scores=None):
         ctx.fork, ctx.seed_offset = fork, seed_offset
         ctx.multi_head = bool(multi_head)
         q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
@@ -1272,7 +1287,7 @@ class _DeformAttnRegion(torch.autograd.Function):
             tables = cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax)
         out, lse = _out_lse(q, heads)
         logits = rid = None
-        if any(ctx.needs_input_grad):
+        if any(ctx.needs_input_grad) or scores is not None:       # (the entry points save the scores and the ids together or not at all)
             logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)
             rid = _score_tiles(q, heads, J, torch.int16)          # the linear piece of every pair, per head
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
@@ -1282,6 +1297,7 @@ class _DeformAttnRegion(torch.autograd.Function):
                       capi.ptr(logits), capi.ptr(rid), B, N, J, *hg, float(scale), float(dropout_p), int(dropout_seed), *dt,
                       *TIMER.events(ev, B * heads * N * J), capi.stream(), capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
+        _keep_scores(scores, logits, lse, heads, groups)
         # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
         if DECISION_TAP is not None:
             ids, tabs = ("region1d_ids", "region1d_tables") if one_d else ("region_ids", "tables")
@@ -1358,7 +1374,7 @@ class _DeformAttnPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
-                table_pmax_fwd, log_distance):
+                table_pmax_fwd, log_distance, scores=None):
         ctx.fork = fork
         ctx.seed_offset = seed_offset           # a device int64 [1] owned by this call (hipGraph replays: deform_attention)
         ctx.log_distance = bool(log_distance)
@@ -1374,7 +1390,7 @@ class _DeformAttnPair(torch.autograd.Function):
         tabfwd = table_pmax_fwd is not None
         ctx.table_pmax = table_pmax_fwd
         ctx.export_masks = None
-        if any(ctx.needs_input_grad):
+        if any(ctx.needs_input_grad) or scores is not None:
             logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)   # 16-bit mode: fp16 scores in both sub-modes
             if not tabfwd:
                 masks = _score_tiles(q, heads, J, torch.int16, 2)           # layer-2 ReLU decisions of the bias MLP (per lane half)
@@ -1398,6 +1414,7 @@ class _DeformAttnPair(torch.autograd.Function):
                           float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), opts), name)
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, masks)
+        _keep_scores(scores, logits, lse, heads, groups)
         if DECISION_TAP is not None:
             DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(),
                                  "masks2": masks if not tabfwd else ctx.export_masks, "B": B, "N": N, "J": J, "heads": heads, "groups": groups,
@@ -1460,7 +1477,8 @@ class _DeformAttnWide(torch.autograd.Function):
     hipGraph as it stands and is run-to-run identical with or without functional.deterministic()."""
 
     @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, log_distance):
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, log_distance,
+                scores=None):
         ctx.fork = fork
         ctx.seed_offset = seed_offset
         ctx.log_distance = bool(log_distance)
@@ -1476,7 +1494,8 @@ class _DeformAttnWide(torch.autograd.Function):
         L = capi.lib()
         out, lse = _out_lse(q, heads)
         # training: the bias tiles are built in logits_t and overwritten in place by the scores; inference: a scratch buffer of that size
-        logits = _score_tiles(q, heads, J, torch.float32) if any(ctx.needs_input_grad) else None
+        # (a call that hands out its scores takes the training form: the same launch, the scores kept)
+        logits = _score_tiles(q, heads, J, torch.float32) if any(ctx.needs_input_grad) or scores is not None else None
         bias = _score_tiles(q, heads, J, torch.float32) if logits is None else None
         capi.check(L.smml_deform_attn_wide_fwd_f32(
             *(capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse)), capi.fptr(logits), capi.fptr(bias), B, N, J, heads,
@@ -1484,6 +1503,7 @@ class _DeformAttnWide(torch.autograd.Function):
             capi.stream(), capi.deform_opts(seed_offset, ctx.log_distance)), "deform_attn_wide_fwd")
         ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed))
         ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits)
+        _keep_scores(scores, logits, lse, heads, groups)
         if DECISION_TAP is not None:
             m1, m2 = wide_decisions(vs, gq, w1, b1, w2, b2, B=B, N=N, J=J, groups=groups, log_distance=ctx.log_distance)
             DECISION_TAP.append({"kind": "attn", "wide": W, "masks1": m1, "masks2": m2, "vs": vs.detach(), "gq": gq.detach(), "B": B, "N": N,
@@ -1629,7 +1649,8 @@ def graph_seed_offset(device, allocate_only: bool = False):
 def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, groups: int, scale: float,
                      dropout_p: float = 0.0, dropout_seed: int = 0, dropout_seed_offset=None, compute_dtype=None, fork=None,
                      cpb_table: bool = False, cpb_table_pmax=None, cpb_table_grid=None, log_distance: bool = True,
-                     cpb_regions=None, cpb_region_pmax=None, cpb_region_prefetch=None, cpb_regions_multi_head: bool = False):
+                     cpb_regions=None, cpb_region_pmax=None, cpb_region_prefetch=None, cpb_regions_multi_head: bool = False,
+                     attn_scores: Optional["AttnScores"] = None):
     """dropout(softmax(scale q k^T + CPB(gq - vs))) v.  q [B, N, H*64], k/v [B, J, H*64], vs [(B G), J, P], gq [N, P].
     dropout_p > 0 applies nn.Dropout semantics to the probabilities with a counter-based mask from dropout_seed
     (+ the value of the device tensor dropout_seed_offset at run time, see graph_seed_offset).
@@ -1649,7 +1670,18 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
     include/smml.h "_mh" entry points; signed-log offsets, either compute mode, no table mode; anything else raises).
     w2 of shape (64, 64) / (128, 128) (dim = 256 / 512 of the modules): the wide family (csrc/deform_attn_wide.hip) - the per-pair MLP in exact
     fp32, fp32-grade core, one or two heads per group, all three position forms; compute_dtype, cpb_table, cpb_regions and
-    cpb_regions_multi_head raise ValueError there."""
+    cpb_regions_multi_head raise ValueError there.
+    attn_scores (an AttnScores, default None: nothing changes): the call also keeps the score tiles and lse its forward writes - with or
+    without grad mode, in the one fused launch - and hands them out there for deform_attention_maps.  The fp32-grade cores only:
+    compute_dtype (2-byte score tiles) and cpb_table raise ValueError."""
+    if attn_scores is not None:
+        if cpb_table:
+            raise ValueError(f"cpb_table={cpb_table!r}: attention maps (attn_scores) are built for the fp32-grade cores, not for the table modes")
+        if compute_dtype is not None:
+            raise ValueError(f"compute_dtype={compute_dtype!r}: attention maps (attn_scores) are built for the fp32-grade cores, whose score tiles "
+                             "are fp32; the 16-bit compute modes save 2-byte tiles")
+        if not isinstance(attn_scores, AttnScores):
+            raise TypeError("attn_scores must be a functional.AttnScores")
     mh = bool(cpb_regions_multi_head) and vs.shape[-1] == 2
     path = deform_path(posdim=vs.shape[-1], heads=heads, groups=groups, keys=k.shape[1], w2_shape=w2.shape, w3_shape=w3.shape,
                        log_distance=log_distance, compute_dtype=compute_dtype, cpb_table=cpb_table, cpb_regions=cpb_regions,
@@ -1658,16 +1690,17 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
                        regions_multi_head=mh)
     if path == "pair_wide":       # width 64 / 128: the region tables, their prefetch and pmax are not consulted
         return _DeformAttnWide.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                     dropout_seed_offset, fork, log_distance)
+                                     dropout_seed_offset, fork, log_distance, attn_scores)
     if path in ("region", "region1d"):
         pmax = cpb_region_pmax
         if path == "region" and pmax is None:      # from the data: one host sync
             pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
         return _DeformAttnRegion.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None, mh)
+                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None, mh,
+                                       attn_scores)
     if path == "pair":
         return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                     dropout_seed_offset, compute_dtype, fork, None, log_distance)
+                                     dropout_seed_offset, compute_dtype, fork, None, log_distance, attn_scores)
     if cpb_table_pmax is None:
         cpb_table_pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
     if path == "pair_table_forward":
@@ -1685,6 +1718,49 @@ def deform_attention_dropout_mask(B: int, N: int, J: int, H: int, dropout_p: flo
     capi.check(L.smml_deform_attn_dropout_mask_f32(capi.fptr(mask), B, N, J, H, float(dropout_p), int(dropout_seed),
                                                    capi.stream(), capi.deform_opts(seed_offset)), "dropout_mask")
     return mask
+
+
+def deform_attention_maps(sink_or_scores, vs=None, *, heads: int, groups: int, grid_hw=None, dense: bool = False):
+    """Where a deform_attention call looked, from the scores it saved (include/smml.h, smml_attn_maps_f32 / smml_attn_splat_f32).
+    sink_or_scores: the AttnScores the call filled, or (logits_t, lse).  The probabilities are the softmax BEFORE dropout.  Returns a dict of
+    detached tensors:
+      key_mass  [B, H, J]        the share of the bag's attention each sampled key receives (rows sum to 1)
+      patch_map [B, G, Hh, Ww]   with 2-D sample positions vs [(B G), J, 2] and grid_hw = (Hh, Ww): the group's mean mass distributed to the
+                                 patch grid with the sampler's corner weights and masks (mass outside the map is dropped: sums to <= 1)
+      attn      [B, H, N, J]     with dense=True: the probabilities themselves (B H N J floats - small bags and tests)
+    No host synchronisation (captures in a hipGraph), no autograd, no float atomics: run-to-run identical."""
+    logits, lse = (sink_or_scores.logits, sink_or_scores.lse) if isinstance(sink_or_scores, AttnScores) else sink_or_scores
+    if logits is None or lse is None:
+        raise ValueError("no scores: pass the AttnScores a deform_attention(..., attn_scores=...) call filled, or (logits_t, lse)")
+    if logits.dtype != torch.float32:
+        raise ValueError(f"attention maps read the fp32 score tiles of the fp32-grade cores; got {logits.dtype} tiles (compute_dtype: the 16-bit "
+                         "compute modes are not supported)")
+    B, H, N = lse.shape
+    J = logits.shape[3]
+    if H != heads or heads % groups or tuple(logits.shape) != (B, H, capi.lib().smml_deform_attn_nst(N) // 32, J, 32):
+        raise ValueError(f"scores of shape {tuple(logits.shape)} / lse {tuple(lse.shape)} do not belong to a call with heads {heads}, groups {groups}")
+    L = capi.lib()
+    with torch.no_grad():
+        logits, lse = _c(logits.detach()), _c(lse.detach())
+        key_mass = torch.empty(B, H, J, device=lse.device, dtype=torch.float32)
+        attn = torch.empty(B, H, N, J, device=lse.device, dtype=torch.float32) if dense else None
+        wsb = L.smml_attn_maps_workspace_bytes(B, N, J, H)
+        ws = torch.empty((wsb + 3) // 4, device=lse.device, dtype=torch.float32)
+        capi.check(L.smml_attn_maps_f32(capi.fptr(logits), capi.fptr(lse), capi.fptr(key_mass), capi.fptr(attn), capi.fptr(ws), wsb, B, N, J, H,
+                                        capi.stream()), "attn_maps")
+        res = {"key_mass": key_mass}
+        if grid_hw is not None and vs is not None and vs.shape[-1] == 2:
+            Hh, Ww = int(grid_hw[0]), int(grid_hw[1])
+            vsc = _c(vs.detach())
+            if tuple(vsc.shape) != (B * groups, J, 2):
+                raise ValueError(f"vs of shape {tuple(vsc.shape)}: expected {(B * groups, J, 2)}")
+            patch_map = torch.empty(B, groups, Hh, Ww, device=lse.device, dtype=torch.float32)
+            capi.check(L.smml_attn_splat_f32(capi.fptr(key_mass), capi.fptr(vsc), capi.fptr(patch_map), B, H, groups, J, Hh, Ww, capi.stream()),
+                       "attn_splat")
+            res["patch_map"] = patch_map
+        if dense:
+            res["attn"] = attn
+    return res
 
 
 # ------------------------------------------------------------------------------------------------

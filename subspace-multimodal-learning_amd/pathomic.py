@@ -126,6 +126,22 @@ class DeformPathomicNet(nn.Module):
             logits = [hazard_tumor, hazard_immune, hazard]
         return features, pathomic_vec_tumor, pathomic_vec_immune, logits, fuse_grads, pathomic_grads_tumor, pathomic_grads_immune
 
+    def attention_maps(self, dense: bool = False, **kwargs):
+        """The normal forward (same kwargs), once, under no_grad -> (its 7-tuple, {"tumor": maps, "immune": maps}) with the maps of each
+        branch's deformable cross-attention (DeformCrossTransMIL.attention_maps).  attn_dim = 2 only."""
+        branches = {"tumor": self.pathomic_net_tumor, "immune": self.pathomic_net_immune}
+        for m in branches.values():
+            m._maps_check()
+        try:
+            for m in branches.values():
+                m._maps_out = ["dense" if dense else True]
+            with torch.no_grad():
+                out = self.forward(**kwargs)
+            return out, {k: m._maps_out[1] for k, m in branches.items()}
+        finally:
+            for m in branches.values():
+                m._maps_out = None
+
 
 def define_net(args):
     """mode 'deformpathomic' of models/model.py:49-79 (init_net with init_type 'max' / 'none' leaves the
