@@ -21,6 +21,9 @@
 
 #include <stddef.h>
 
+/* what smml_abi_version() returns.  2: per-call SmmlDeformOpts instead of per-thread setters, region entry points */
+#define SMML_ABI_VERSION 2
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -191,8 +194,6 @@ int smml_bilinear_sample_bwd_det_f32(const float* x, const float* vs, const floa
 int smml_bilinear_corners_f32(const float* vs, int* cx, int* cy, unsigned char* cm, int n, int Hh, int Ww,
                               int posdim, void* stream);
 
-#ifndef SMML_DEFORM_OPTS_DEFINED
-#define SMML_DEFORM_OPTS_DEFINED
 /* Optional behaviour of ONE fused deformable-attention launch (trailing `opts` argument of the entry points below; NULL = all defaults).
  * Passed by the caller with every call: the library keeps no per-thread or global launch state. */
 typedef struct SmmlDeformOpts {
@@ -208,7 +209,6 @@ typedef struct SmmlDeformOpts {
   int region_lds_cap;                    /* tests: the region entry points keep only regions with an id below this in LDS and take the others from
                                             global memory (the path of parameter sets with more than 2048 linear regions); 0 = the default (2048) */
 } SmmlDeformOpts;
-#endif
 
 /* ------------------------------------------------------------------------------------------------
  * Fused deformable cross-attention core: softmax(scale q k^T + CPB(gq - vs)) v with the continuous

@@ -11,6 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
+INCLUDE = os.path.join(os.path.dirname(PKG), "include")   # smml.h: csrc/smml_common.h includes it, so every definition is checked against it
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libsmml_hip.so")
 ARCH = "gfx950"
@@ -40,7 +41,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, "smml.h")]
     jobs = []
     for s in sources():
         src = os.path.join(CSRC, s)
@@ -51,7 +52,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     def compile_one(job):
         src, obj = job
         cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(os.path.basename(src), []), *os.environ.get("SMML_HIPCC_FLAGS", "").split(),
-               "-I", CSRC, "-c", src, "-o", obj]
+               "-I", CSRC, "-I", INCLUDE, "-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr}")
@@ -87,7 +88,7 @@ def build_host_sanitized(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(PKG, "build", "host_san")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, "smml.h")]
     san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
     jobs = []
     for s in sources():
@@ -97,7 +98,7 @@ def build_host_sanitized(force: bool = False, verbose: bool = True) -> str:
 
     def compile_one(job):
         src, obj = job
-        r = subprocess.run([hipcc, "-O1", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", *san, "-I", CSRC, "-c", src, "-o", obj],
+        r = subprocess.run([hipcc, "-O1", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", *san, "-I", CSRC, "-I", INCLUDE, "-c", src, "-o", obj],
                            capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"sanitized host build failed on {src}:\n{r.stderr}")

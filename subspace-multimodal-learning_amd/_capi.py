@@ -6,137 +6,86 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-# SMML_LIB: measurement hook - load another build of the same C-ABI (tests/build_variants.py writes them to lib/variants/)
+# SMML_LIB: measurement hook - load another build of the same C-ABI (tests/tools/build_variants.py writes them to lib/variants/)
 LIB_PATH = os.environ.get("SMML_LIB") or os.path.join(_PKG, "lib", "libsmml_hip.so")
 
-_f = C.c_void_p          # device pointers travel as void*
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "smml.h")
 
 
 class DeformOpts(C.Structure):
-    """SmmlDeformOpts of include/smml.h: optional behaviour of ONE fused deformable-attention launch, passed with the call."""
-    _fields_ = [("seed_offset", C.c_void_p), ("raw_distance", C.c_int), ("mask_table", C.c_void_p), ("mask_table_pmax", C.c_float),
-                ("export_masks", C.c_void_p), ("region_lds_cap", C.c_int)]
+    """SmmlDeformOpts of include/smml.h: optional behaviour of ONE fused deformable-attention launch, passed with the call.
+    _fields_ are the header's, set below."""
 
 
-_o = C.POINTER(DeformOpts)
-_i, _ll, _fl, _sz = C.c_int, C.c_longlong, C.c_float, C.c_size_t
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "float": C.c_float, "size_t": C.c_size_t}
 
-ABI_VERSION = 2          # smml_abi_version() of the library this binding is written against
 
-# name -> (restype, argtypes); mirrors include/smml.h one to one
-SIGNATURES = {
-    "smml_last_error": (C.c_char_p, []),
-    "smml_abi_version": (_i, []),
-    "smml_device_check": (_i, [_i]),
-    "smml_gemm_f32": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _ll, _ll, _ll, _ll,
-                           _ll, _ll, _ll, _ll, _i, _i, _ll, _i, _i, _i, _fl, _fl, _f]),
-    "smml_gemm_f32_det_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "smml_gemm_f32_det": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _ll, _ll, _ll, _ll,
-                               _ll, _ll, _ll, _ll, _i, _i, _ll, _i, _i, _i, _fl, _fl, _f, _sz, _f]),
-    "smml_gemm_force_generic": (None, [_i]),
-    "smml_gemm_set_mode": (None, [_i]),
-    "smml_gemm_get_mode": (_i, []),
-    "smml_gemm_set_small_tile": (None, [_i]),
-    "smml_gemm_b16": (_i, [_f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _i, _i, _i, _f]),
-    "smml_gemm_b16_set_tile": (None, [_i]),
-    "smml_gemm_b16_set_slice_major": (None, [_i]),
-    "smml_gemm_b16_batched": (_i, [_f, _f, _f, _f, _i, _i, _i, _ll, _ll, _ll, _i, _i, _i, _i, _ll, _ll, _ll, _f]),
-    "smml_attn16_fwd_workspace_bytes": (_sz, [_i, _i, _i]),
-    "smml_attn16_fwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _fl, _i, _i, _i, _f]),
-    "smml_attn16_set_fewkeys": (None, [_i]),
-    "smml_attn16_set_query_blocks": (None, [_i]),
-    "smml_attn16_fwd_b16": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _fl, _i, _ll, _ll, _ll, _ll, _ll, _ll, _f]),
-    "smml_attn16_bwd_b16": (_i, [_f] * 11 + [_sz, _i, _i, _i, _i, _fl, _i] + [_ll] * 9 + [_i, _f]),
-    "smml_attn16_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
-    "smml_attn16_bwd_f32": (_i, [_f] * 10 + [_f, _sz, _i, _i, _i, _i, _fl, _i, _i, _f]),
-    "smml_layernorm_fwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _ll, _i, _fl, _f]),
-    "smml_layernorm_bwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _ll, _i, _ll, _fl, _i, _f]),
-    "smml_layernorm_bwd_det_workspace_bytes": (_sz, [_ll, _i]),
-    "smml_layernorm_bwd_det_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _ll, _i, _ll, _fl, _i, _f, _sz, _f]),
-    "smml_colsum_f32": (_i, [_f, _f, _i, _ll, _i, _fl, _f]),
-    "smml_colsum_det_workspace_bytes": (_sz, [_i, _ll, _i]),
-    "smml_colsum_det_f32": (_i, [_f, _f, _i, _ll, _i, _fl, _f, _sz, _f]),
-    "smml_orth_loss_f32": (_i, [_f] * 10 + [_i, _i, _fl, _f]),
-    "smml_batchloss_tail_f32": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _fl, _f]),
-    "smml_relu_bwd_f32": (_i, [_f, _f, _f, _ll, _f]),
-    "smml_offsets_out_len": (_i, [_i, _i, _i]),
-    "smml_offsets_fwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _f]),
-    "smml_offsets_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "smml_offsets_bwd_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _i, _f]),
-    "smml_bilinear_sample_fwd_f32": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
-    "smml_bilinear_sample_bwd_f32": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f]),
-    "smml_bilinear_sample_bwd_det_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "smml_bilinear_sample_bwd_det_f32": (_i, [_f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _f]),
-    "smml_bilinear_corners_f32": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
-    "smml_deform_attn_nst": (_i, [_i]),
-    "smml_deform_attn_fwd_f32": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_dropout_mask_f32": (_i, [_f, _i, _i, _i, _i, _fl, C.c_ulonglong, _f] + [_o]),
-    "smml_deform_attn_relu1_masks": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f] + [_o]),
-    "smml_attn_maps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "smml_attn_maps_f32": (_i, [_f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _f]),
-    "smml_attn_splat_f32": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _f]),
-    "smml_deform_attn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "smml_deform_attn_bwd_f32": (_i, [_f] * 27 + [_f, _sz, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_wide_fwd_f32": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_wide_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "smml_deform_attn_wide_bwd_f32": (_i, [_f] * 26 + [_f, _sz, _i, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_wide_decisions": (_i, [_f] * 7 + [_i, _i, _i, _i, _i, _i, _f] + [_o]),
-    "smml_cpb_regions_bytes": (_sz, []),
-    "smml_cpb_regions_build": (_i, [_f] * 6 + [_fl, _f, _sz, _f]),
-    "smml_deform_attn_region_fwd_f32": (_i, [_f] * 16 + [_i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_region_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "smml_deform_attn_region_bwd_f32": (_i, [_f] * 28 + [_f, _sz, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_cpb_regions1d_bytes": (_sz, []),
-    "smml_cpb_regions1d_build": (_i, [_f] * 6 + [_i, _fl, _f, _sz, _f]),
-    "smml_deform_attn_region1d_fwd_f32": (_i, [_f] * 10 + [_i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_region1d_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "smml_deform_attn_region1d_bwd_f32": (_i, [_f] * 22 + [_f, _sz, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_region_fwd": (_i, [_f] * 16 + [_i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_region_bwd": (_i, [_f] * 28 + [_f, _sz, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_cpb_regions_mh_build": (_i, [_f] * 6 + [_i, _fl, _f, _sz, _f]),
-    "smml_deform_attn_region_mh_fwd_f32": (_i, [_f] * 16 + [_i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn_region_mh_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "smml_deform_attn_region_mh_bwd_f32": (_i, [_f] * 28 + [_f, _sz, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_region_mh_fwd": (_i, [_f] * 16 + [_i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_region_mh_bwd": (_i, [_f] * 28 + [_f, _sz, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_fwd": (_i, [_f] * 15 + [_i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_deform_attn16_bwd": (_i, [_f] * 27 + [_f, _sz, _i, _i, _i, _i, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_cpb_mask_table_cells": (_i, [_i]),
-    "smml_cpb_mask_table": (_i, [_f, _f, _f, _f, _f, _i, _fl, _f]),
-    "smml_deform_attn_table_points": (_i, [_i]),
-    "smml_deform_attn_table_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "smml_deform_attn_table_fwd": (_i, [_f] * 9 + [_i, _i, _i, _i, _i, _i, _i, _fl, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_deform_attn_table_bwd": (_i, [_f] * 16 + [_f, _sz, _i, _i, _i, _i, _i, _i, _i, _fl, _i, _i, _fl, _fl, C.c_ulonglong, _i, _f, _f, _f] + [_o]),
-    "smml_softmax_fwd_f32": (_i, [_f, _f, _ll, _i, _f]),
-    "smml_softmax_bwd_f32": (_i, [_f, _f, _f, _ll, _i, _f]),
-    "smml_tile_rows_f32": (_i, [_f, _f, _ll, _i, _i, _fl, _f]),
-    "smml_segment_mean_b16": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f]),
-    "smml_segment_mean_bwd_add_b16": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f]),
-    "smml_resconv_b16": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _i, _f]),
-    "smml_resconv_wgrad_b16": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _f]),
-    "smml_newton_schulz_set_fast": (None, [_i]),
-    "smml_newton_schulz_saved_floats": (_sz, [_i, _i, _i, _i]),
-    "smml_newton_schulz_scratch_floats": (_sz, [_i, _i, _i, _i]),
-    "smml_newton_schulz_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
-    "smml_newton_schulz_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f]),
-    "smml_resconv_fwd_f32": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f]),
-    "smml_resconv_bwd_f32": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
-    "smml_dwconv7_fwd_f32": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
-    "smml_dwconv7_bwd_weight_f32": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
-    "smml_grad_modulate_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
-    "smml_grad_modulate_survival_f32": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
-    "smml_fixdim_indices": (_i, [_f, _ll, _ll, _f]),
-    "smml_fixdim_gather_bf16": (_i, [_f, _ll, _f, _i, _ll, _i, _f]),
-    "smml_event_create": (C.c_void_p, []),
-    "smml_event_destroy": (_i, [_f]),
-    "smml_event_record": (_i, [_f, _f]),
-    "smml_event_elapsed_ms": (_i, [_f, _f, C.POINTER(C.c_float)]),
-}
+def _ctype(ctext: str, where: str, ret: bool = False):
+    """ctypes type of a C type as include/smml.h writes it: device and host pointers travel as void*, scalars by the table above."""
+    t = " ".join(ctext.replace("*", " * ").split())
+    if t == "void" and ret:
+        return None
+    if t == "const char *" and ret:
+        return C.c_char_p
+    if t == "const SmmlDeformOpts *":
+        return C.POINTER(DeformOpts)
+    if re.fullmatch(r"(const )?\w+( \w+)* \*", t):
+        return C.c_void_p
+    if t not in _SCALARS:
+        raise RuntimeError(f"include/smml.h: type `{ctext.strip()}` of `{where}` is not one the ctypes binding knows")
+    return _SCALARS[t]
+
+
+def _declarator(text: str, where: str):
+    """`type name` -> (ctypes type, name)"""
+    m = re.fullmatch(r"\s*([\w\s]*[\w*])\s*\b([A-Za-z_]\w*)\s*", text)
+    if not m or m.group(2) in ("int", "long", "float", "void", "unsigned", "size_t", "char", "short", "const"):
+        raise RuntimeError(f"include/smml.h: cannot read `{text.strip()}` of `{where}` as `type name`")
+    return _ctype(m.group(1), where), m.group(2)
+
+
+def parse_prototypes(text: str) -> dict:
+    """name -> (restype, [argtypes]) for C text that holds prototypes `ret smml_name(type name, ...);` and nothing else besides
+    comments, preprocessor lines and the extern "C" bracket.  Strict: whatever it cannot read raises, with the offending text."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    sigs = {}
+    *protos, tail = text.split(";")
+    if tail.strip():
+        raise RuntimeError(f"include/smml.h: `{' '.join(tail.split())}` does not end in `;`")
+    for proto in protos:
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(smml_\w+)\s*\(([^()]*)\)\s*", proto)
+        if not m or m.group(2) in sigs:
+            raise RuntimeError(f"include/smml.h: cannot read `{' '.join(proto.split())}` as one prototype `ret smml_name(type name, ...)`")
+        ret, name, params = m.groups()
+        args = [] if params.strip() == "void" else [_declarator(p, name)[0] for p in params.split(",")]
+        sigs[name] = (_ctype(ret, name, ret=True), args)
+    return sigs
+
+
+def parse_header(text: str):
+    """(SMML_ABI_VERSION, the fields of SmmlDeformOpts, name -> (restype, [argtypes])) of the text of include/smml.h"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    abi = re.search(r"^[ \t]*#[ \t]*define[ \t]+SMML_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
+    struct = re.search(r"typedef\s+struct\s+SmmlDeformOpts\s*\{(.*?)\}\s*SmmlDeformOpts\s*;", text, re.S)
+    if not abi or not struct:
+        raise RuntimeError("include/smml.h: SMML_ABI_VERSION or struct SmmlDeformOpts not found")
+    fields = [_declarator(f, "SmmlDeformOpts")[::-1] for f in struct.group(1).split(";") if f.strip()]
+    return int(abi.group(1)), fields, parse_prototypes(text[:struct.start()] + text[struct.end():])
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it (it ships with the repository, next to the package)")
+# ABI_VERSION: smml_abi_version() of the library this binding is for; SIGNATURES: name -> (restype, argtypes), as the header declares them
+with open(HEADER_PATH) as _h:
+    ABI_VERSION, DeformOpts._fields_, SIGNATURES = parse_header(_h.read())
 
 _lib: Optional[C.CDLL] = None
 

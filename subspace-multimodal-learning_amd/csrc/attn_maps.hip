@@ -13,8 +13,6 @@
 // (their bits may be anything, NaN included, so they are not multiplied by zero).
 #include "smml_common.h"
 
-extern "C" int smml_deform_attn_nst(int N);
-
 namespace {
 
 constexpr int AM_TILES = 8;                 // 32-query tiles per workgroup (256 queries): 8 independent 16-byte loads in flight per lane

@@ -30,8 +30,6 @@
 #include "cpb_regions.h"
 #include "cpb_regions1d.h"
 
-extern "C" int smml_deform_attn_nst(int N);
-
 namespace {
 
 
@@ -1034,8 +1032,7 @@ int bwd_dq_dkv(const char* fn, const float* q, const float* k, const float* v, c
 
 }  // namespace
 
-// bwd_dq_dkv for the wide position-bias family (deform_attn_wide.hip): plain argument types only, because the types of deform_common.h live
-// in an unnamed namespace per translation unit.  Not part of the C-ABI.
+// bwd_dq_dkv for the wide position-bias family (deform_attn_wide.hip; declared in deform_common.h)
 int smml_wide_bwd_dq_dkv(const char* fn, const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
                          const float* logits_t, float* dlogits_t, float* dq, float* dk, float* dv, float* wsf, int B, int N, int J, int H,
                          float scale, float dropout_p, unsigned long long dropout_seed, const SmmlDeformOpts* opts, void* stream) {

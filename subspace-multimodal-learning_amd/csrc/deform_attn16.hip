@@ -21,11 +21,6 @@
 #include "deform16_types.h"
 #include "cpb_regions.h"
 
-extern "C" {
-int smml_deform_attn_nst(int N);
-size_t smml_deform_attn_bwd_workspace_bytes(int B, int N, int J, int H);
-}
-
 namespace {
 
 constexpr int FWD16_WPS = 2;      // waves per SIMD the forward is register-budgeted for

@@ -23,12 +23,6 @@
 //   g1 = [x1 > 0] d h1 (x1 recomputed by the evaluator's own layer-1 function), d vs per key; one lane per channel: d b1, d W1.
 #include "deform_common.h"
 
-extern "C" int smml_deform_attn_nst(int N);
-// deform_attn.hip: backward passes 1 and 2 (d scores, dq; dk, dv) of every fp32-grade backward
-int smml_wide_bwd_dq_dkv(const char* fn, const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
-                         const float* logits_t, float* dlogits_t, float* dq, float* dk, float* dv, float* wsf, int B, int N, int J, int H,
-                         float scale, float dropout_p, unsigned long long dropout_seed, const SmmlDeformOpts* opts, void* stream);
-
 namespace {
 
 // LDS image of the MLP (floats): w2t[in][out] (rows of W + 1) | w1x[W] | w1y[W] | b1[W] | b2[W] | w3[2][W]

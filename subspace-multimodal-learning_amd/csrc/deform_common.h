@@ -6,6 +6,13 @@
 #pragma once
 #include "smml_common.h"
 
+// deform_attn.hip: backward passes 1 and 2 (d scores, dq; dk, dv) of every fp32-grade backward, for the wide position-bias family
+// (deform_attn_wide.hip).  Internal, C++ linkage, not part of the C-ABI; plain argument types only, because the types below live in an
+// unnamed namespace per translation unit.
+int smml_wide_bwd_dq_dkv(const char* fn, const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
+                         const float* logits_t, float* dlogits_t, float* dq, float* dk, float* dv, float* wsf, int B, int N, int J, int H,
+                         float scale, float dropout_p, unsigned long long dropout_seed, const SmmlDeformOpts* opts, void* stream);
+
 namespace {
 
 // log, exp and reciprocal are the hardware approximations (v_log_f32, v_exp_f32, v_rcp_f32: 1 ulp), not the libm forms.

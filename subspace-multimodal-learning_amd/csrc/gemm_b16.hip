@@ -407,9 +407,6 @@ extern "C" void smml_gemm_b16_set_slice_major(int on) { g_b16_slice_major = on; 
 // C = A B^T (trans = 0: A [M, K], B [N, K], leading dimensions lda / ldb in elements) or C = A^T B (trans = 1: A [K, M], B [K, N]);
 // A, B bf16; C bf16 (out_bf16 = 1, ldc in bf16 elements) or fp32; bias (fp32 [N], may be null) is added once.  splitk > 1: fp32 output only,
 // the K range is cut into splitk slices whose partial products are ADDED to C atomically - the caller zeroes C first.
-extern "C" int smml_gemm_b16_batched(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda,
-                                     long long ldb, long long ldc, int trans, int out_bf16, int splitk, int nb, long long sa, long long sb,
-                                     long long sc, void* stream);
 extern "C" int smml_gemm_b16(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long long lda,
                              long long ldb, long long ldc, int trans, int out_bf16, int splitk, void* stream) {
   return smml_gemm_b16_batched(A, B, C, bias, M, N, K, lda, ldb, ldc, trans, out_bf16, splitk, 1, 0, 0, 0, stream);

@@ -13,12 +13,6 @@
 #include <atomic>     // process-wide measurement switches (set once from the environment or a test hook): plain atomics, no launch state
 #include "smml_common.h"
 
-extern "C" int smml_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual, int M, int N, int K,
-                             long long sam, long long sak, long long sbk, long long sbn, long long ldc, long long ldr, int nb0, int nb1,
-                             long long sa0, long long sa1, long long sb0, long long sb1, long long sc0, long long sc1, long long sbias0,
-                             long long sbias1, int bias_mode, int rows_per_bias, long long bias_ld, int act, int splitk, int accumulate,
-                             float alpha, float beta, void* stream);
-
 #define SMML_TRY(call)      \
   do {                      \
     int rc_ = (call);       \

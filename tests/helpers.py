@@ -33,12 +33,24 @@ Tolerance policy (north_star: "fp32 within 1e-4 relative", integer paths bit-exa
 import atexit
 import importlib
 import os
+import re
 
 import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 smml = importlib.import_module("subspace-multimodal-learning_amd")
+HEADER = os.path.join(os.path.dirname(GOLDEN), os.pardir, "include", "smml.h")
+
+
+def header_arity():
+    """name -> number of parameters of every prototype of include/smml.h, read with a plain regular expression (independent of the
+    parser of _capi.py, which the host tests hold against it)"""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    decls = re.findall(r"\b(int|size_t|void|const char\*)\s+(smml_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)
+    return {name: (0 if body.strip() in ("", "void") else len(body.split(","))) for _, name, body in decls}
+
+
 synth = smml.synth
 
 TOL = 1e-4

@@ -1,9 +1,11 @@
-"""CPU: the C-ABI library loads and exports every symbol include/smml.h declares (no compute calls),
-the ctypes table mirrors the header, and the host-side mirror keeps the reference's interface."""
+"""CPU: the C-ABI library loads and exports every symbol include/smml.h declares (no compute calls), the header is the one place
+the C-ABI is written down (the compiler holds the definitions of csrc/ against it, the ctypes table is derived from it), and the
+host-side mirror keeps the reference's interface."""
 import ctypes
 import inspect
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -37,7 +39,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_kernels_have_no_compile_time_switches():
     """One code path per kernel: no preprocessor conditional of csrc/ names an SMML* macro (a -D measurement variant; the retired ones are
-    listed in HISTORY.md) - only the include guard of the SmmlDeformOpts struct, which smml_common.h shares with include/smml.h."""
+    listed in HISTORY.md).  No exemption: the SmmlDeformOpts struct is defined in include/smml.h alone and needs no guard."""
     csrc = os.path.join(ROOT, "subspace-multimodal-learning_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
     assert len(files) >= 15
@@ -47,7 +49,7 @@ def test_kernels_have_no_compile_time_switches():
         for line in txt.split("\n"):
             m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
             if m:
-                found += [f"{f}: {line.strip()}" for name in re.findall(r"\bSMML\w*", m.group(2)) if name != "SMML_DEFORM_OPTS_DEFINED"]
+                found += [f"{f}: {line.strip()}" for name in re.findall(r"\bSMML\w*", m.group(2))]
     assert not found, "\n".join(found)
 
 
@@ -60,6 +62,73 @@ def test_argument_counts_match_header():
         body = m.group(1).strip()
         n = 0 if body in ("", "void") else body.count(",") + 1
         assert n == len(args), f"{name}: header has {n} parameters, ctypes table {len(args)}"
+
+
+CSRC = os.path.join(ROOT, "subspace-multimodal-learning_amd", "csrc")
+
+
+def test_compiler_checks_definitions_against_header(tmp_path):
+    """Every translation unit sees include/smml.h through smml_common.h, so a definition whose parameter types drift from its declaration
+    no longer compiles (extern "C" symbols carry no types: it would link and load).  Host pass only, nothing is run."""
+    rc = {}
+    for ty in ("long long", "int"):
+        src = tmp_path / f"nst_{ty.replace(' ', '_')}.hip"
+        src.write_text(f'#include "smml_common.h"\nextern "C" int smml_deform_attn_nst({ty} N) {{ return 0; }}\n')
+        rc[ty] = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-fsyntax-only", "--cuda-host-only", "-std=c++17",
+                                 "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src)], capture_output=True, text=True)
+    assert rc["int"].returncode == 0, rc["int"].stderr
+    assert rc["long long"].returncode != 0 and "conflicting types for 'smml_deform_attn_nst'" in rc["long long"].stderr, rc["long long"].stderr
+
+
+def test_no_second_copy_of_the_abi_in_csrc():
+    """csrc/ holds definitions only: no body-less prototype of a name include/smml.h declares, no second SmmlDeformOpts."""
+    names = set(smml.SIGNATURES)
+    found = []
+    for f in sorted(os.listdir(CSRC)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        txt = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(CSRC, f)).read(), flags=re.S)
+        # a prototype: the name after a type (a word or '*'; not `return`, an operator or '('), a parenthesis-free parameter list, then ';'
+        found += [f"{f}: prototype of {m.group(2)}" for m in re.finditer(r"([\w*]+)\s+(smml_\w+)\s*\([^(){};]*\)\s*;", txt)
+                  if m.group(2) in names and m.group(1) != "return"]
+        if re.search(r"struct\s+SmmlDeformOpts\s*\{", txt):
+            found.append(f"{f}: defines struct SmmlDeformOpts")
+    assert not found, "\n".join(found)
+    assert re.search(r'^#include "smml\.h"', open(os.path.join(CSRC, "smml_common.h")).read(), re.M)
+
+
+def test_bindings_are_derived_from_header():
+    """Entries whose types are easy to get wrong, as the parser of _capi.py reads them from include/smml.h."""
+    C, S, capi = ctypes, smml.SIGNATURES, smml._capi
+    gemm = S["smml_gemm_f32"][1]
+    assert len(gemm) == 33 and gemm[8] is C.c_longlong and gemm[-1] is C.c_void_p
+    assert gemm[:8] == [C.c_void_p] * 5 + [C.c_int] * 3 and gemm[30:32] == [C.c_float] * 2
+    assert S["smml_last_error"] == (C.c_char_p, [])
+    assert S["smml_deform_attn_bwd_workspace_bytes"] == (C.c_size_t, [C.c_int] * 4)
+    fwd = S["smml_deform_attn_fwd_f32"][1]
+    assert fwd[23] is C.c_ulonglong and fwd[-1] is C.POINTER(capi.DeformOpts) and len(fwd) == 28      # dropout_seed, opts
+    assert S["smml_gemm_set_mode"] == (None, [C.c_int])
+    assert S["smml_event_create"] == (C.c_void_p, [])
+    assert [n for n, _ in capi.DeformOpts._fields_] == ["seed_offset", "raw_distance", "mask_table", "mask_table_pmax", "export_masks",
+                                                        "region_lds_cap"]
+    assert [t for _, t in capi.DeformOpts._fields_] == [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int]
+    assert C.sizeof(capi.DeformOpts) == 48          # LP64: pointer, int + pad, pointer, float + pad, pointer, int + pad
+    abi, fields, sigs = capi.parse_header(open(capi.HEADER_PATH).read())
+    assert abi == 2 and fields == capi.DeformOpts._fields_ and sigs == S
+
+
+@pytest.mark.parametrize("proto", ["int smml_x(const float* a, double x);",                    # a type the binding does not know
+                                   "int smml_x(const float* a, int);", "int smml_x(const float*, int n);",
+                                   "int smml_x(long long, int n);", "int smml_x(unsigned long long);",       # unnamed parameters
+                                   "int smml_x(int (*cb)(int), void* stream);",             # a function pointer
+                                   "double smml_x(int n);", "int smml_x(int n)", "int smml_x(int n); int smml_x(int n);",
+                                   "int other_x(int n);", "struct S { int a; };"])
+def test_header_parser_refuses_what_it_does_not_understand(proto):
+    parse = smml._capi.parse_prototypes
+    assert parse("/* c */ int smml_ok(const float* a, long long n, void* stream); // d\nvoid smml_v(void);") == {
+        "smml_ok": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]), "smml_v": (None, [])}
+    with pytest.raises(RuntimeError, match="smml.h"):
+        parse("int smml_ok(int n);\n" + proto)
 
 
 def test_error_channel_without_gpu():

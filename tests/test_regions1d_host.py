@@ -3,28 +3,19 @@ declared, exported and bound with matching arity; the module / model switches ex
 path does not support raises instead of falling back."""
 import argparse
 import inspect
-import re
-import os
 
 import pytest
 import torch
 
-from helpers import smml
+from helpers import header_arity, smml
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Fh = smml.functional
 NEW = ("smml_cpb_regions1d_bytes", "smml_cpb_regions1d_build", "smml_deform_attn_region1d_fwd_f32",
        "smml_deform_attn_region1d_bwd_workspace_bytes", "smml_deform_attn_region1d_bwd_f32")
 
 
-def _declared():
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smml.h")).read(), flags=re.S)
-    decls = re.findall(r"\b(int|size_t|void|const char\*)\s+(smml_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)
-    return {name: (0 if body.strip() in ("", "void") else len(body.split(","))) for _, name, body in decls}
-
-
 def test_region1d_symbols_declared_exported_and_bound():
-    decl = _declared()
+    decl = header_arity()
     sig = smml._capi.SIGNATURES
     L = smml.lib()
     for name in NEW:

@@ -3,29 +3,20 @@
 (functional.deform_path(regions_multi_head=...)) and the module keyword with their defaults; every combination the path does not support
 raises instead of falling back."""
 import inspect
-import os
-import re
 
 import pytest
 import torch
 
-from helpers import smml
+from helpers import header_arity, smml
 from test_deform_routing import CASES, expected
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Fh = smml.functional
 NEW = ("smml_cpb_regions_mh_build", "smml_deform_attn_region_mh_fwd_f32", "smml_deform_attn_region_mh_bwd_workspace_bytes",
        "smml_deform_attn_region_mh_bwd_f32", "smml_deform_attn16_region_mh_fwd", "smml_deform_attn16_region_mh_bwd")
 
 
-def _declared():
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smml.h")).read(), flags=re.S)
-    decls = re.findall(r"\b(int|size_t|void|const char\*)\s+(smml_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S)
-    return {name: (0 if body.strip() in ("", "void") else len(body.split(","))) for _, name, body in decls}
-
-
 def test_mh_symbols_declared_exported_and_bound():
-    decl = _declared()
+    decl = header_arity()
     sig = smml._capi.SIGNATURES
     L = smml.lib()
     for name in NEW:

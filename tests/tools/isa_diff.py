@@ -13,9 +13,10 @@ b = importlib.import_module("subspace-multimodal-learning_amd._build")
 
 
 def assembly(csrc, src, out):
+    include = os.path.join(csrc, os.path.relpath(b.INCLUDE, b.CSRC))      # include/smml.h of the same tree
     if not os.path.exists(os.path.join(csrc, src)):
         return ""
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), "-I", csrc, "-S", "--cuda-device-only",
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), "-I", csrc, "-I", include, "-S", "--cuda-device-only",
            os.path.join(csrc, src), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -44,7 +45,7 @@ if __name__ == "__main__":
     rev = sys.argv[1]
     csrc_rel = os.path.relpath(b.CSRC, ROOT)
     with tempfile.TemporaryDirectory() as tmp:
-        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, csrc_rel], capture_output=True, check=True).stdout
+        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, csrc_rel, os.path.relpath(b.INCLUDE, ROOT)], capture_output=True, check=True).stdout
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(tmp)
         old_csrc = os.path.join(tmp, csrc_rel)
         srcs = sys.argv[2:] or sorted(set(b.sources()) | {f for f in os.listdir(old_csrc) if f.endswith(".hip")})

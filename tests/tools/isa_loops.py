@@ -9,7 +9,7 @@ rest = sys.argv[2:]
 want = [a for a in rest if not a.startswith("-")]
 extra = [a for a in rest if a.startswith("-")]
 out = os.path.join(tempfile.mkdtemp(), src[:-4] + ".s")
-subprocess.run(["/opt/rocm/bin/hipcc", *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), *extra, "-I", b.CSRC, "-S", "--cuda-device-only",
+subprocess.run(["/opt/rocm/bin/hipcc", *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), *extra, "-I", b.CSRC, "-I", b.INCLUDE, "-S", "--cuda-device-only",
                 os.path.join(b.CSRC, src), "-o", out], check=True, stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]

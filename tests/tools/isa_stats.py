@@ -9,7 +9,7 @@ b = importlib.import_module("subspace-multimodal-learning_amd._build")
 src = sys.argv[1]
 extra = sys.argv[2:]
 out = os.path.join(tempfile.mkdtemp(), src[:-4] + ".s")
-cmd = ["/opt/rocm/bin/hipcc", *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), *extra, "-I", b.CSRC, "-S", "--cuda-device-only", os.path.join(b.CSRC, src), "-o", out]
+cmd = ["/opt/rocm/bin/hipcc", *b.FLAGS, *b.EXTRA_FLAGS.get(src, []), *extra, "-I", b.CSRC, "-I", b.INCLUDE, "-S", "--cuda-device-only", os.path.join(b.CSRC, src), "-o", out]
 subprocess.run(cmd, check=True)
 txt = open(out).read()
 print("asm:", out)
