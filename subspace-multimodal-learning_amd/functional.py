@@ -973,7 +973,7 @@ TABLE_FORWARD_MASKS = __import__("os").environ.get("SMML_TABFWD_MASKS", "table")
 
 
 # fp32-grade path, 2-D positions: the position bias per LINEAR REGION of its MLP (csrc/cpb_regions.h, include/smml.h) - exact, and the
-# default wherever it applies (signed-log offsets, one head per offset group, J <= 1024).  SMML_CPB_REGIONS=0 keeps the per-pair MLP
+# default wherever it applies (signed-log offsets, one head per offset group, J <= REGION_MAX_KEYS).  SMML_CPB_REGIONS=0 keeps the per-pair MLP
 # kernels (the cross-check of tests/test_gpu_regions.py, and the path of every other configuration).
 CPB_REGIONS = __import__("os").environ.get("SMML_CPB_REGIONS", "1") != "0"
 REGION_MAX_KEYS = 16384      # RG_MAX_KEYS of csrc/cpb_regions.h
@@ -1196,11 +1196,6 @@ def _check_core(q, heads: int, w2=None):
         raise RuntimeError("the position-bias kernels are built for a hidden width of 32 (dim = 128)")
 
 
-def _out_lse(q, heads: int):
-    B, N, _ = q.shape
-    return torch.empty_like(q), torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
-
-
 def _score_tiles(q, heads: int, J: int, dtype, *inner):
     """A score-shaped tensor, stored per 32-query tile (include/smml.h): [B, H, nst / 32, J, *inner, 32]."""
     B, N, _ = q.shape
@@ -1218,14 +1213,47 @@ class AttnScores:
         self.heads = self.groups = None
 
 
-def _keep_scores(scores, logits, lse, heads: int, groups: int) -> None:
+def _core_inputs(ctx, tensors, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork, w2=None):
+    """Prologue of a fused core's forward: the call's settings on ctx, the shape rules of every core -> (the contiguous tensors, m16).
+    seed_offset: a device int64 [1] owned by this call (hipGraph replays: deform_attention)."""
+    ctx.fork, ctx.seed_offset = fork, seed_offset
+    tensors = tuple(_c(t) for t in tensors)
+    _check_core(tensors[0], heads, w2)
+    m16 = _dtype16(compute_dtype)
+    ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
+    return tensors, m16
+
+
+def _core_outputs(ctx, q, heads: int, J: int, m16, scores=None):
+    """out, lse and the score tiles (fp32; 16-bit core: fp16) - the tiles only where a backward or an AttnScores sink will read them (the
+    entry points save the scores and their side tensor together or not at all)."""
+    B, N, _ = q.shape
+    out, lse = torch.empty_like(q), torch.empty(B, heads, N, device=q.device, dtype=torch.float32)
+    keep = any(ctx.needs_input_grad) or scores is not None
+    return out, lse, (_score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16) if keep else None)
+
+
+def _core_done(ctx, inputs, out, lse, logits, side=(), scores=None, tap=None):
+    """Epilogue of a fused core's forward: saves (*inputs, out, lse, logits, *side) for the backward, fills the AttnScores sink, appends
+    the call's DECISION_TAP entry - the keys of every core plus `tap`, the core's own (tests/helpers.py reads them)."""
+    ctx.save_for_backward(*inputs, out, lse, logits, *side)
+    heads, groups = ctx.cfg[:2]
     if scores is not None:
         scores.logits, scores.lse, scores.heads, scores.groups = logits.detach(), lse.detach(), int(heads), int(groups)
+    if DECISION_TAP is not None:
+        q, k, _, vs, gq = inputs[:5]
+        DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "B": q.shape[0], "N": q.shape[1], "J": k.shape[1],
+                             "heads": heads, "groups": groups, **tap})
+    return out
 
 
-def _dscores(logits, m16):
-    """The d scores of a backward: the scores' shape, fp32 (fp32-grade core) or bf16 (16-bit core)."""
-    return torch.empty(logits.shape, device=logits.device, dtype=torch.float32 if m16 is None else torch.bfloat16)
+def _core_backward(ctx, dout, logits, like, wsb: int, ws_dtype=torch.float32):
+    """The buffers of a fused core's backward: dout (contiguous), the d scores (the scores' shape; fp32, 16-bit core: bf16), one
+    gradient per tensor of `like`, the workspace of wsb bytes."""
+    dout = _c(dout)
+    dlogits = torch.empty(logits.shape, device=logits.device, dtype=torch.float32 if ctx.cfg[5] is None else torch.bfloat16)
+    grads = tuple(torch.empty_like(t) for t in like)
+    return dout, dlogits, grads, torch.empty(wsb if ws_dtype == torch.uint8 else (wsb + 3) // 4, device=dout.device, dtype=ws_dtype)
 
 
 def _grads(ctx, *grads):
@@ -1237,95 +1265,36 @@ def _grads(ctx, *grads):
     return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
-# (1-D, multi-head, 16-bit) -> the region entry points' stem in include/smml.h ("smml_" + stem + "_fwd" / "_bwd", "_f32" behind the fp32-grade
-# ones), their workspace-size function, the TIMER events of the forward and of the bias backward, the stem of the capi.check names
-_REGION_ENTRY = {
-    (True, False, False): ("deform_attn_region1d", "smml_deform_attn_region1d_bwd_workspace_bytes", "deform_region1d_fwd", "cpb_region1d_bwd"),
-    (False, False, False): ("deform_attn_region", "smml_deform_attn_region_bwd_workspace_bytes", "deform_region_fwd", "cpb_region_bwd"),
-    (False, False, True): ("deform_attn16_region", "smml_deform_attn_region_bwd_workspace_bytes", "deform16_region_fwd", "cpb16_region_bwd"),
-    (False, True, False): ("deform_attn_region_mh", "smml_deform_attn_region_mh_bwd_workspace_bytes", "deform_region_mh_fwd", "cpb_region_mh_bwd"),
-    (False, True, True): ("deform_attn16_region_mh", "smml_deform_attn_region_mh_bwd_workspace_bytes", "deform16_region_mh_fwd",
-                          "cpb16_region_mh_bwd"),
+# (the core deform_path names, multi-head, 16-bit) -> the stems of its forward's and its backward's entry point in include/smml.h ("smml_" +
+# stem + "_fwd" / "_bwd", "_f32" behind the fp32-grade ones; stem + "_fwd" / "_bwd" is the capi.check name too), the workspace-size function
+# of the backward, the TIMER events of the forward and of the bias backward
+_WS = "smml_deform_attn_{}bwd_workspace_bytes"
+_CORE_ENTRY = {
+    ("pair", False, False): ("deform_attn", "deform_attn", _WS.format(""), "deform_attn_fwd", "cpb_bwd"),
+    ("pair", False, True): ("deform_attn16", "deform_attn16", _WS.format(""), "deform16_fwd", "cpb16_bwd"),
+    ("pair_table_forward", False, True): ("deform_attn_table", "deform_attn16", _WS.format(""), "deform_table_fwd", "cpb16_bwd"),
+    ("pair_wide", False, False): ("deform_attn_wide", "deform_attn_wide", _WS.format("wide_"), "deform_wide_fwd", "cpb_wide_bwd"),
+    ("table", False, True): ("deform_attn_table", "deform_attn_table", _WS.format("table_"), "deform_table_fwd", "cpb_table_bwd"),
+    ("region1d", False, False): ("deform_attn_region1d", "deform_attn_region1d", _WS.format("region1d_"), "deform_region1d_fwd", "cpb_region1d_bwd"),
+    ("region", False, False): ("deform_attn_region", "deform_attn_region", _WS.format("region_"), "deform_region_fwd", "cpb_region_bwd"),
+    ("region", False, True): ("deform_attn16_region", "deform_attn16_region", _WS.format("region_"), "deform16_region_fwd", "cpb16_region_bwd"),
+    ("region", True, False): ("deform_attn_region_mh", "deform_attn_region_mh", _WS.format("region_mh_"), "deform_region_mh_fwd", "cpb_region_mh_bwd"),
+    ("region", True, True): ("deform_attn16_region_mh", "deform_attn16_region_mh", _WS.format("region_mh_"), "deform16_region_mh_fwd",
+                             "cpb16_region_mh_bwd"),
 }
 
 
-def _region_entry(ctx, vs, direction: str):
-    """Of this call's region launch in `direction` ('fwd' / 'bwd'): the C entry point, its heads / groups and dtype arguments, the
-    workspace-size function and its arguments, the TIMER event and the capi.check name."""
-    heads, groups, m16 = ctx.cfg[0], ctx.cfg[1], ctx.cfg[5]
-    one_d = vs.shape[-1] == 1
-    stem, ws, ev_fwd, ev_bwd = _REGION_ENTRY[(one_d, ctx.multi_head, m16 is not None)]
-    L = capi.lib()
-    fn = getattr(L, f"smml_{stem}_{direction}" + ("" if m16 is not None else "_f32"))
-    hg = (heads, groups) if one_d or ctx.multi_head else (heads,)
-    return (fn, hg, () if m16 is None else (m16[0],), getattr(L, ws), (heads, groups) if ctx.multi_head else (heads,),
-            ev_fwd if direction == "fwd" else ev_bwd, f"{stem}_{direction}")
+def _core_entry(ctx):
+    return _CORE_ENTRY[(ctx.path, ctx.multi_head, ctx.cfg[5] is not None)]
 
 
-class _DeformAttnRegion(torch.autograd.Function):
-    """The fused core with the position bias per linear region of its MLP (include/smml.h): 2-D (csrc/cpb_regions.h; fp32-grade or, with
-    compute_dtype, the 16-bit core) or 1-D per linear piece (csrc/cpb_regions1d.h; fp32-grade core).  pmax: half-width of the tables'
-    square (2-D) / index grid (1-D; None: the span of the breakpoints); prefetch: a RegionPrefetch of the 2-D tables, if any.
-    multi_head (2-D): the entry points of one or two heads per offset group (include/smml.h, "_mh")."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
-                pmax, prefetch, multi_head=False, scores=None):
-        ctx.fork, ctx.seed_offset = fork, seed_offset
-        ctx.multi_head = bool(multi_head)
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
-        B, N, _ = q.shape
-        J = k.shape[1]
-        one_d = vs.shape[-1] == 1
-        _check_core(q, heads, w2)
-        m16 = _dtype16(compute_dtype)
-        if one_d:
-            tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
-        elif prefetch is not None and prefetch.matches(w1, b1, w2, b2, w3, b3, pmax):
-            tables = prefetch.join()                 # built beside the layers in front of the attention (RegionPrefetch)
-        else:
-            tables = cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax)
-        out, lse = _out_lse(q, heads)
-        logits = rid = None
-        if any(ctx.needs_input_grad) or scores is not None:       # (the entry points save the scores and the ids together or not at all)
-            logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)
-            rid = _score_tiles(q, heads, J, torch.int16)          # the linear piece of every pair, per head
-        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
-        fn, hg, dt, _, _, ev, name = _region_entry(ctx, vs, "fwd")
-        w = () if one_d else tuple(capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3))        # (the 1-D tables carry the parameters)
-        capi.check(fn(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), *w, capi.ptr(tables), capi.fptr(out), capi.fptr(lse),
-                      capi.ptr(logits), capi.ptr(rid), B, N, J, *hg, float(scale), float(dropout_p), int(dropout_seed), *dt,
-                      *TIMER.events(ev, B * heads * N * J), capi.stream(), capi.deform_opts(seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
-        ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables)
-        _keep_scores(scores, logits, lse, heads, groups)
-        # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
-        if DECISION_TAP is not None:
-            ids, tabs = ("region1d_ids", "region1d_tables") if one_d else ("region_ids", "tables")
-            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(), "w2": w2.detach(),
-                                 "b2": b2.detach(), "masks2": None, ids: rid, tabs: tables, "B": B, "N": N, "J": J, "heads": heads,
-                                 "groups": groups, "table_pmax": None, "log_distance": True})
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, rid, tables = ctx.saved_tensors
-        heads, _, scale, dropout_p, dropout_seed, m16 = ctx.cfg
-        B, N, _ = q.shape
-        J = k.shape[1]
-        dout = _c(dout)
-        dlogits = _dscores(logits, m16)
-        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
-        grads = (capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs), capi.fptr(dw1), capi.fptr(db1), capi.fptr(dw2), capi.fptr(db2),
-                 capi.fptr(dw3), capi.fptr(db3))
-        fn, hg, dt, ws_bytes, ws_hg, ev, name = _region_entry(ctx, vs, "bwd")
-        wsb = ws_bytes(B, N, J, *ws_hg)
-        ws = torch.empty(wsb, device=q.device, dtype=torch.uint8)
-        w = () if vs.shape[-1] == 1 else tuple(capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3))
-        capi.check(fn(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), *w, capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
-                      capi.fptr(lse), capi.ptr(logits), capi.ptr(rid), capi.ptr(dlogits), *grads, capi.ptr(ws), wsb, B, N, J, *hg, scale, dropout_p,
-                      dropout_seed, *dt, *TIMER.events(ev, B * heads * N * J), capi.stream(),
-                      capi.deform_opts(ctx.seed_offset, region_lds_cap=REGION_LDS_CAP)), name)
-        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
+def _launch(ctx, direction: str, q, k, opts, *args):
+    """This call's launch in `direction` ('fwd' / 'bwd'): every entry point ends with (TIMER events, stream, opts)."""
+    e = _core_entry(ctx)
+    stem, ev = (e[0], e[3]) if direction == "fwd" else (e[1], e[4])
+    fn = getattr(capi.lib(), f"smml_{stem}_{direction}" + ("_f32" if ctx.cfg[5] is None else ""))
+    pairs = q.shape[0] * ctx.cfg[0] * q.shape[1] * k.shape[1]
+    capi.check(fn(*args, *TIMER.events(ev, pairs), capi.stream(), opts), f"{stem}_{direction}")
 
 
 _REGION_STREAMS = {}
@@ -1367,96 +1336,6 @@ class RegionPrefetch:
         return self.tables
 
 
-class _DeformAttnPair(torch.autograd.Function):
-    """The fused core with the per-pair position-bias MLP (csrc/deform_attn.hip; with compute_dtype csrc/deform_attn16.hip).
-    table_pmax_fwd (cpb_table='forward', 16-bit): the forward takes its bias from the table, the backward takes layer 2's decisions from
-    a mask table (or recomputes them per pair: TABLE_FORWARD_MASKS)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork,
-                table_pmax_fwd, log_distance, scores=None):
-        ctx.fork = fork
-        ctx.seed_offset = seed_offset           # a device int64 [1] owned by this call (hipGraph replays: deform_attention)
-        ctx.log_distance = bool(log_distance)
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
-        B, N, _ = q.shape
-        J = k.shape[1]
-        posdim = vs.shape[-1]
-        _check_core(q, heads, w2)
-        L = capi.lib()
-        m16 = _dtype16(compute_dtype)
-        out, lse = _out_lse(q, heads)
-        logits = masks = None
-        tabfwd = table_pmax_fwd is not None
-        ctx.table_pmax = table_pmax_fwd
-        ctx.export_masks = None
-        if any(ctx.needs_input_grad) or scores is not None:
-            logits = _score_tiles(q, heads, J, torch.float32 if m16 is None else torch.float16)   # 16-bit mode: fp16 scores in both sub-modes
-            if not tabfwd:
-                masks = _score_tiles(q, heads, J, torch.int16, 2)           # layer-2 ReLU decisions of the bias MLP (per lane half)
-            elif DECISION_TAP is not None:            # tests: the backward writes the decisions it recomputed here
-                ctx.export_masks = _score_tiles(q, heads, J, torch.int16, 2).zero_()
-        opts = capi.deform_opts(seed_offset, ctx.log_distance)
-        pairs = B * heads * N * J
-        qkv = (capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq))
-        w = [capi.fptr(t) for t in (w1, b1, w2, b2, w3, b3)]
-        if tabfwd:
-            points = L.smml_deform_attn_table_points(posdim)
-            with torch.no_grad():
-                table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=posdim, pmax=table_pmax_fwd, device=q.device)
-            capi.check(L.smml_deform_attn_table_fwd(*qkv, capi.fptr(table), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups,
-                                                    posdim, points, float(table_pmax_fwd), float(scale), float(dropout_p), int(dropout_seed), m16[0],
-                                                    *TIMER.events("deform_table_fwd", pairs), capi.stream(), opts), "deform_attn_table_fwd")
-        else:
-            fn, ev, name, dt = ((L.smml_deform_attn_fwd_f32, "deform_attn_fwd", "deform_attn_fwd", ()) if m16 is None else
-                                (L.smml_deform_attn16_fwd, "deform16_fwd", "deform_attn16_fwd", (m16[0],)))
-            capi.check(fn(*qkv, *w, capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(masks), B, N, J, heads, groups, posdim, float(scale),
-                          float(dropout_p), int(dropout_seed), *dt, *TIMER.events(ev, pairs), capi.stream(), opts), name)
-        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16)
-        ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, masks)
-        _keep_scores(scores, logits, lse, heads, groups)
-        if DECISION_TAP is not None:
-            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "w1": w1.detach(), "b1": b1.detach(),
-                                 "masks2": masks if not tabfwd else ctx.export_masks, "B": B, "N": N, "J": J, "heads": heads, "groups": groups,
-                                 "table_pmax": table_pmax_fwd, "log_distance": ctx.log_distance})
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, masks = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
-        B, N, _ = q.shape
-        J = k.shape[1]
-        posdim = vs.shape[-1]
-        L = capi.lib()
-        dout = _c(dout)
-        dlogits = _dscores(logits, m16)
-        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
-        wsb = L.smml_deform_attn_bwd_workspace_bytes(B, N, J, heads)
-        ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
-        pairs = B * heads * N * J
-        fwd = [capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, dout, lse)]
-        grads = [capi.fptr(t) for t in (dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3)]
-        if m16 is None:
-            capi.check(L.smml_deform_attn_bwd_f32(
-                *fwd, capi.fptr(logits), capi.ptr(masks), capi.fptr(dlogits), *grads, capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale,
-                dropout_p, dropout_seed, *TIMER.events("cpb_bwd", pairs), capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance)),
-                "deform_attn_bwd")
-        else:
-            mtab = None
-            if masks is None and TABLE_FORWARD_MASKS == "table":
-                # table-forward call: layer-2 decisions from a mask table (include/smml.h) built from the current weights - one small launch
-                cells = L.smml_cpb_mask_table_cells(posdim)
-                mtab = torch.empty(cells ** posdim, device=q.device, dtype=torch.int32)
-                capi.check(L.smml_cpb_mask_table(capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.ptr(mtab), posdim,
-                                                 float(ctx.table_pmax), capi.stream()), "cpb_mask_table")
-            capi.check(L.smml_deform_attn16_bwd(
-                *fwd, capi.ptr(logits), capi.ptr(masks), capi.ptr(dlogits), *grads, capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, scale,
-                dropout_p, dropout_seed, m16[0], *TIMER.events("cpb16_bwd", pairs), capi.stream(),
-                capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)), "deform_attn16_bwd")
-        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
-
-
 def wide_decisions(vs, gq, w1, b1, w2, b2, *, B: int, N: int, J: int, groups: int, log_distance: bool = True):
     """Tests: the ReLU decisions of the wide position-bias MLP (width 64 / 128) exactly as its forward and backward take them
     (smml_deform_attn_wide_decisions) -> (m1, m2) bool [(B groups), N, J, W]: [x1 > 0], [x2 > 0] per pair and hidden channel."""
@@ -1468,67 +1347,6 @@ def wide_decisions(vs, gq, w1, b1, w2, b2, *, B: int, N: int, J: int, groups: in
     bits = ((words[..., None] >> torch.arange(32, device=vs.device, dtype=torch.int32)) & 1).bool()      # [..., 2, W / 32, 32]
     bits = bits.reshape(B * groups, N, J, 2, W)
     return bits[..., 0, :], bits[..., 1, :]
-
-
-class _DeformAttnWide(torch.autograd.Function):
-    """The fp32-grade fused core for a bias MLP of width 64 / 128 (csrc/deform_attn_wide.hip): the forward evaluates the MLP once per pair
-    into bias tiles and runs the attention kernel on them, the backward is the dq / dkv passes of the width-32 core followed by the wide
-    bias backward, which recomputes the MLP - no ReLU mask is saved.  No host synchronisation and no float atomics: the call captures in a
-    hipGraph as it stands and is run-to-run identical with or without functional.deterministic()."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed, seed_offset, fork, log_distance,
-                scores=None):
-        ctx.fork = fork
-        ctx.seed_offset = seed_offset
-        ctx.log_distance = bool(log_distance)
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = (_c(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3))
-        B, N, _ = q.shape
-        J = k.shape[1]
-        posdim = vs.shape[-1]
-        W = w2.shape[0]
-        _check_core(q, heads)
-        if tuple(w1.shape) != (W, posdim) or tuple(w3.shape) != (heads // groups, W) or tuple(b1.shape) != (W,) or tuple(b2.shape) != (W,):
-            raise RuntimeError(f"the wide position-bias MLP is {posdim} -> {W} -> {W} -> heads // groups; got w1 {tuple(w1.shape)}, "
-                               f"w3 {tuple(w3.shape)}")
-        L = capi.lib()
-        out, lse = _out_lse(q, heads)
-        # training: the bias tiles are built in logits_t and overwritten in place by the scores; inference: a scratch buffer of that size
-        # (a call that hands out its scores takes the training form: the same launch, the scores kept)
-        logits = _score_tiles(q, heads, J, torch.float32) if any(ctx.needs_input_grad) or scores is not None else None
-        bias = _score_tiles(q, heads, J, torch.float32) if logits is None else None
-        capi.check(L.smml_deform_attn_wide_fwd_f32(
-            *(capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse)), capi.fptr(logits), capi.fptr(bias), B, N, J, heads,
-            groups, W, posdim, float(scale), float(dropout_p), int(dropout_seed), *TIMER.events("deform_wide_fwd", B * heads * N * J),
-            capi.stream(), capi.deform_opts(seed_offset, ctx.log_distance)), "deform_attn_wide_fwd")
-        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed))
-        ctx.save_for_backward(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits)
-        _keep_scores(scores, logits, lse, heads, groups)
-        if DECISION_TAP is not None:
-            m1, m2 = wide_decisions(vs, gq, w1, b1, w2, b2, B=B, N=N, J=J, groups=groups, log_distance=ctx.log_distance)
-            DECISION_TAP.append({"kind": "attn", "wide": W, "masks1": m1, "masks2": m2, "vs": vs.detach(), "gq": gq.detach(), "B": B, "N": N,
-                                 "J": J, "heads": heads, "groups": groups, "log_distance": ctx.log_distance})
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed = ctx.cfg
-        B, N, _ = q.shape
-        J = k.shape[1]
-        W = w2.shape[0]
-        L = capi.lib()
-        dout = _c(dout)
-        dlogits = _dscores(logits, None)
-        dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3 = (torch.empty_like(t) for t in (q, k, v, vs, w1, b1, w2, b2, w3, b3))
-        wsb = L.smml_deform_attn_wide_bwd_workspace_bytes(B, N, J, heads, groups, W)
-        ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
-        capi.check(L.smml_deform_attn_wide_bwd_f32(
-            *(capi.fptr(t) for t in (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, dout, lse, logits, dlogits, dq, dk, dv, dvs, dw1, db1, dw2,
-                                     db2, dw3, db3)), capi.fptr(ws), wsb, B, N, J, heads, groups, W, vs.shape[-1], scale, dropout_p, dropout_seed,
-            *TIMER.events("cpb_wide_bwd", B * heads * N * J), capi.stream(), capi.deform_opts(ctx.seed_offset, ctx.log_distance)),
-            "deform_attn_wide_bwd")
-        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1564,58 +1382,153 @@ def cpb_table_fn(w1, b1, w2, b2, w3, b3, *, posdim: int, pmax: float, device):
     return t.reshape(1, -1) if t.shape[1] == 1 else t.t().contiguous()
 
 
+class _DeformAttnMLP(torch.autograd.Function):
+    """The fused cores that differentiate the six tensors of the position-bias MLP; `path` is what deform_path answered:
+    'pair'  the per-pair MLP (csrc/deform_attn.hip; with compute_dtype csrc/deform_attn16.hip), saving layer 2's ReLU decisions;
+    'pair_table_forward'  (16-bit) the forward takes its bias from the table of half-width pmax, the backward takes layer 2's decisions
+        from a mask table (or recomputes them per pair: TABLE_FORWARD_MASKS);
+    'region' / 'region1d'  the bias per linear region (2-D, csrc/cpb_regions.h; fp32-grade or 16-bit core; multi_head: the "_mh" entry
+        points of one or two heads per offset group) / per linear piece (1-D, csrc/cpb_regions1d.h; fp32-grade core), saving every pair's
+        region id.  pmax: half-width of the tables' square / index grid (1-D; None: the span of the breakpoints); prefetch: a
+        RegionPrefetch of the 2-D tables, if any;
+    'pair_wide'  a bias MLP of width 64 / 128 (csrc/deform_attn_wide.hip; fp32-grade core): the forward evaluates the MLP once per pair
+        into bias tiles and runs the attention kernel on them, the backward is the dq / dkv passes of the width-32 core followed by the
+        wide bias backward, which recomputes the MLP - no ReLU mask is saved.  No host synchronisation and no float atomics: the call
+        captures in a hipGraph as it stands and is run-to-run identical with or without functional.deterministic()."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, path, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype,
+                fork, log_distance, pmax, prefetch, multi_head, scores):
+        ctx.path, ctx.multi_head, ctx.log_distance = path, bool(multi_head), bool(log_distance)
+        wide, region = path == "pair_wide", path in ("region", "region1d")
+        inputs, m16 = _core_inputs(ctx, (q, k, v, vs, gq, w1, b1, w2, b2, w3, b3), heads, groups, scale, dropout_p, dropout_seed, seed_offset,
+                                   compute_dtype, fork, None if wide else w2)
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = inputs
+        (B, N, _), J, posdim, W = q.shape, k.shape[1], vs.shape[-1], w2.shape[0]
+        if wide and (tuple(w1.shape) != (W, posdim) or tuple(w3.shape) != (heads // groups, W) or tuple(b1.shape) != (W,)
+                     or tuple(b2.shape) != (W,)):
+            raise RuntimeError(f"the wide position-bias MLP is {posdim} -> {W} -> {W} -> heads // groups; got w1 {tuple(w1.shape)}, "
+                               f"w3 {tuple(w3.shape)}")
+        L = capi.lib()
+        tables = None
+        if path == "region1d":
+            tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
+        elif region and prefetch is not None and prefetch.matches(w1, b1, w2, b2, w3, b3, pmax):
+            tables = prefetch.join()                 # built beside the layers in front of the attention (RegionPrefetch)
+        elif region:
+            tables = cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax)
+        out, lse, logits = _core_outputs(ctx, q, heads, J, m16, scores)
+        ctx.table_pmax = pmax if path == "pair_table_forward" else None
+        ctx.export_masks = side = None               # side: the score-shaped tensor the core saves beside the scores
+        qkv, mlp = tuple(capi.fptr(t) for t in inputs[:5]), tuple(capi.fptr(t) for t in inputs[5:])
+        run = (float(scale), float(dropout_p), int(dropout_seed)) + (() if m16 is None else (m16[0],))
+        if region:
+            if logits is not None:
+                side = _score_tiles(q, heads, J, torch.int16)                 # the linear piece of every pair, per head
+            hg = (heads, groups) if path == "region1d" or ctx.multi_head else (heads,)
+            args = (*qkv, *(mlp if path == "region" else ()), capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(side),
+                    B, N, J, *hg, *run)                                       # (the 1-D tables carry the parameters)
+        elif path == "pair":
+            if logits is not None:
+                side = _score_tiles(q, heads, J, torch.int16, 2)              # layer-2 ReLU decisions of the bias MLP (per lane half)
+            args = (*qkv, *mlp, capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(side), B, N, J, heads, groups, posdim, *run)
+        elif wide:
+            # training: the bias tiles are built in logits_t and overwritten in place by the scores; inference: a scratch buffer of that size
+            # (a call that hands out its scores takes the training form: the same launch, the scores kept)
+            bias = _score_tiles(q, heads, J, torch.float32) if logits is None else None
+            args = (*qkv, *mlp, capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.fptr(bias), B, N, J, heads, groups, W, posdim, *run)
+        else:
+            if logits is not None and DECISION_TAP is not None:               # tests: the backward writes the decisions it recomputed here
+                ctx.export_masks = _score_tiles(q, heads, J, torch.int16, 2).zero_()
+            with torch.no_grad():
+                table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=posdim, pmax=pmax, device=q.device)
+            args = (*qkv, capi.fptr(table), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups, posdim,
+                    L.smml_deform_attn_table_points(posdim), float(pmax), *run)
+        _launch(ctx, "fwd", q, k, capi.deform_opts(seed_offset, ctx.log_distance, region_lds_cap=REGION_LDS_CAP if region else 0), *args)
+        tap = None
+        if DECISION_TAP is not None and region:
+            # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
+            ids, tabs = ("region1d_ids", "region1d_tables") if path == "region1d" else ("region_ids", "tables")
+            tap = {"w1": w1.detach(), "b1": b1.detach(), "w2": w2.detach(), "b2": b2.detach(), "masks2": None, ids: side, tabs: tables,
+                   "table_pmax": None, "log_distance": True}
+        elif DECISION_TAP is not None and wide:
+            m1, m2 = wide_decisions(vs, gq, w1, b1, w2, b2, B=B, N=N, J=J, groups=groups, log_distance=ctx.log_distance)
+            tap = {"wide": W, "masks1": m1, "masks2": m2, "log_distance": ctx.log_distance}
+        elif DECISION_TAP is not None:
+            tap = {"w1": w1.detach(), "b1": b1.detach(), "masks2": side if path == "pair" else ctx.export_masks, "table_pmax": ctx.table_pmax,
+                   "log_distance": ctx.log_distance}
+        return _core_done(ctx, inputs, out, lse, logits, (side, tables), scores, tap)
+
+    @staticmethod
+    def backward(ctx, dout):
+        *inputs, out, lse, logits, side, tables = ctx.saved_tensors
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = inputs
+        heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
+        (B, N, _), J, posdim, W = q.shape, k.shape[1], vs.shape[-1], w2.shape[0]
+        path, region = ctx.path, ctx.path in ("region", "region1d")
+        L = capi.lib()
+        ws_dims = (heads, groups, W) if path == "pair_wide" else (heads, groups) if ctx.multi_head else (heads,)
+        wsb = getattr(L, _core_entry(ctx)[2])(B, N, J, *ws_dims)
+        dout, dlogits, grads, ws = _core_backward(ctx, dout, logits, (q, k, v, vs, w1, b1, w2, b2, w3, b3), wsb,
+                                                  torch.uint8 if region else torch.float32)
+        gp = tuple(capi.fptr(g) for g in grads)
+        run = (scale, dropout_p, dropout_seed) + (() if m16 is None else (m16[0],))
+        opts = capi.deform_opts(ctx.seed_offset, ctx.log_distance, region_lds_cap=REGION_LDS_CAP if region else 0)
+        if region:
+            hg = (heads, groups) if path == "region1d" or ctx.multi_head else (heads,)
+            args = (*(capi.fptr(t) for t in inputs[:5 if path == "region1d" else 11]), capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
+                    capi.fptr(lse), capi.ptr(logits), capi.ptr(side), capi.ptr(dlogits), *gp, capi.ptr(ws), wsb, B, N, J, *hg, *run)
+        elif path == "pair_wide":
+            args = (*(capi.fptr(t) for t in (*inputs, out, dout, lse, logits, dlogits)), *gp, capi.fptr(ws), wsb, B, N, J, heads, groups, W,
+                    posdim, *run)
+        else:
+            mtab = None
+            if path == "pair_table_forward" and TABLE_FORWARD_MASKS == "table":
+                # layer-2 decisions from a mask table (include/smml.h) built from the current weights - one small launch
+                cells = L.smml_cpb_mask_table_cells(posdim)
+                mtab = torch.empty(cells ** posdim, device=q.device, dtype=torch.int32)
+                capi.check(L.smml_cpb_mask_table(capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.ptr(mtab), posdim,
+                                                 float(ctx.table_pmax), capi.stream()), "cpb_mask_table")
+            if m16 is not None:
+                opts = capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)
+            args = (*(capi.fptr(t) for t in (*inputs, out, dout, lse)), capi.ptr(logits), capi.ptr(side), capi.ptr(dlogits), *gp, capi.fptr(ws),
+                    wsb, B, N, J, heads, groups, posdim, *run)
+        _launch(ctx, "bwd", q, k, opts, *args)
+        return _grads(ctx, *grads[:4], None, *grads[4:])
+
+
 class _DeformAttnTable(torch.autograd.Function):
     """The 16-bit core with the position bias interpolated from `table` (include/smml.h, table mode); differentiates the table, which
     cpb_table_fn carries back to the MLP."""
 
     @staticmethod
     def forward(ctx, q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork, pmax, grid):
-        ctx.fork, ctx.seed_offset = fork, seed_offset
-        ctx.grid = tuple(int(x) for x in grid) if grid else (0, 0)
-        q, k, v, vs, gq, table = _c(q), _c(k), _c(v), _c(vs), _c(gq), _c(table)
-        B, N, _ = q.shape
-        J = k.shape[1]
-        posdim = vs.shape[-1]
-        _check_core(q, heads)
-        L = capi.lib()
-        m16 = _dtype16(compute_dtype)
-        points = L.smml_deform_attn_table_points(posdim)
+        ctx.path, ctx.multi_head = "table", False
+        inputs, m16 = _core_inputs(ctx, (q, k, v, vs, gq, table), heads, groups, scale, dropout_p, dropout_seed, seed_offset, compute_dtype, fork)
+        q, k, v, vs, gq, table = inputs
+        (B, N, _), J, posdim = q.shape, k.shape[1], vs.shape[-1]
+        points = capi.lib().smml_deform_attn_table_points(posdim)
         if tuple(table.shape) != (heads // groups, points ** posdim):
             raise RuntimeError(f"table must be [{heads // groups}, {points ** posdim}] (got {tuple(table.shape)})")
-        out, lse = _out_lse(q, heads)
-        logits = _score_tiles(q, heads, J, torch.float16) if any(ctx.needs_input_grad) else None
-        capi.check(L.smml_deform_attn_table_fwd(capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(table),
-                                                capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups, posdim, points,
-                                                float(pmax), float(scale), float(dropout_p), int(dropout_seed), m16[0],
-                                                *TIMER.events("deform_table_fwd", B * heads * N * J), capi.stream(), capi.deform_opts(seed_offset)),
-                   "deform_attn_table_fwd")
-        ctx.cfg = (heads, groups, float(scale), float(dropout_p), int(dropout_seed), m16, points, float(pmax))
-        ctx.save_for_backward(q, k, v, vs, gq, table, out, lse, logits)
-        if DECISION_TAP is not None:       # no per-pair ReLU decisions in this mode: the MLP runs on grid points only
-            DECISION_TAP.append({"kind": "attn", "vs": vs.detach(), "gq": gq.detach(), "masks2": None, "B": B, "N": N, "J": J,
-                                 "heads": heads, "groups": groups, "table_pmax": float(pmax)})
-        return out
+        ctx.table = (points, float(pmax)) + (tuple(int(x) for x in grid) if grid else (0, 0))
+        out, lse, logits = _core_outputs(ctx, q, heads, J, m16)
+        _launch(ctx, "fwd", q, k, capi.deform_opts(seed_offset), *(capi.fptr(t) for t in (*inputs, out, lse)), capi.ptr(logits), B, N, J, heads,
+                groups, posdim, points, float(pmax), float(scale), float(dropout_p), int(dropout_seed), m16[0])
+        # no per-pair ReLU decisions in this mode: the MLP runs on grid points only
+        return _core_done(ctx, inputs, out, lse, logits, tap={"masks2": None, "table_pmax": float(pmax)})
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, vs, gq, table, out, lse, logits = ctx.saved_tensors
-        heads, groups, scale, dropout_p, dropout_seed, m16, points, pmax = ctx.cfg
-        B, N, _ = q.shape
-        J = k.shape[1]
-        posdim = vs.shape[-1]
-        L = capi.lib()
-        dout = _c(dout)
-        dlogits = _dscores(logits, m16)
-        dq, dk, dv, dvs, dtable = (torch.empty_like(t) for t in (q, k, v, vs, table))
-        wsb = L.smml_deform_attn_table_bwd_workspace_bytes(B, N, J, heads, posdim)
-        ws = torch.empty((wsb + 3) // 4, device=q.device, dtype=torch.float32)
-        capi.check(L.smml_deform_attn_table_bwd(
-            capi.fptr(q), capi.fptr(k), capi.fptr(v), capi.fptr(vs), capi.fptr(gq), capi.fptr(table), capi.fptr(out), capi.fptr(dout),
-            capi.fptr(lse), capi.ptr(logits), capi.ptr(dlogits), capi.fptr(dq), capi.fptr(dk), capi.fptr(dv), capi.fptr(dvs),
-            capi.fptr(dtable), capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, points, pmax, ctx.grid[0], ctx.grid[1], scale, dropout_p,
-            dropout_seed, m16[0],
-            *TIMER.events("cpb_table_bwd", B * heads * N * J), capi.stream(), capi.deform_opts(ctx.seed_offset)), "deform_attn_table_bwd")
-        return _grads(ctx, dq, dk, dv, dvs, None, dtable)
+        *inputs, out, lse, logits = ctx.saved_tensors
+        q, k, v, vs, gq, table = inputs
+        heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
+        (B, N, _), J, posdim = q.shape, k.shape[1], vs.shape[-1]
+        wsb = getattr(capi.lib(), _core_entry(ctx)[2])(B, N, J, heads, posdim)
+        dout, dlogits, grads, ws = _core_backward(ctx, dout, logits, (q, k, v, vs, table), wsb)
+        _launch(ctx, "bwd", q, k, capi.deform_opts(ctx.seed_offset), *(capi.fptr(t) for t in (*inputs, out, dout, lse)), capi.ptr(logits),
+                capi.ptr(dlogits), *(capi.fptr(g) for g in grads), capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, *ctx.table, scale,
+                dropout_p, dropout_seed, m16[0])
+        return _grads(ctx, *grads[:4], None, grads[4])
 
 
 def table_pmax(gq_bound: float, vs_bound: float) -> float:
@@ -1688,27 +1601,16 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
                        region_pmax_given=cpb_region_pmax is not None,
                        capturing=cpb_region_pmax is None and q.is_cuda and torch.cuda.is_current_stream_capturing(),
                        regions_multi_head=mh)
-    if path == "pair_wide":       # width 64 / 128: the region tables, their prefetch and pmax are not consulted
-        return _DeformAttnWide.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                     dropout_seed_offset, fork, log_distance, attn_scores)
-    if path in ("region", "region1d"):
-        pmax = cpb_region_pmax
-        if path == "region" and pmax is None:      # from the data: one host sync
-            pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
-        return _DeformAttnRegion.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                       dropout_seed_offset, compute_dtype, fork, pmax, cpb_region_prefetch if path == "region" else None, mh,
-                                       attn_scores)
-    if path == "pair":
-        return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                     dropout_seed_offset, compute_dtype, fork, None, log_distance, attn_scores)
-    if cpb_table_pmax is None:
-        cpb_table_pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
-    if path == "pair_table_forward":
-        return _DeformAttnPair.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, heads, groups, scale, dropout_p, dropout_seed,
-                                     dropout_seed_offset, compute_dtype, fork, cpb_table_pmax, log_distance)
-    table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=vs.shape[-1], pmax=cpb_table_pmax, device=q.device)
-    return _DeformAttnTable.apply(q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, dropout_seed_offset,
-                                  compute_dtype, fork, cpb_table_pmax, cpb_table_grid)
+    # the half-width the core's tables need, if it has any (width 64 / 128: the region tables, their prefetch and pmax are not consulted)
+    pmax = {"region": cpb_region_pmax, "region1d": cpb_region_pmax, "pair_table_forward": cpb_table_pmax, "table": cpb_table_pmax}.get(path)
+    if pmax is None and path in ("region", "pair_table_forward", "table"):      # from the data: one host sync
+        pmax = table_pmax(float(gq.detach().abs().max()), float(vs.detach().abs().max()))
+    if path == "table":
+        table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=vs.shape[-1], pmax=pmax, device=q.device)
+        return _DeformAttnTable.apply(q, k, v, vs, gq, table, heads, groups, scale, dropout_p, dropout_seed, dropout_seed_offset,
+                                      compute_dtype, fork, pmax, cpb_table_grid)
+    return _DeformAttnMLP.apply(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, path, heads, groups, scale, dropout_p, dropout_seed, dropout_seed_offset,
+                                compute_dtype, fork, log_distance, pmax, cpb_region_prefetch if path == "region" else None, mh, attn_scores)
 
 
 def deform_attention_dropout_mask(B: int, N: int, J: int, H: int, dropout_p: float, dropout_seed: int, device, seed_offset=None):

@@ -195,14 +195,10 @@ class Decisions:
         self.m1 = self.m2 = None
         self.regions = None
         if a.get("region_ids") is not None:   # region kernels (csrc/cpb_regions.h): a pair's decisions are the ReLU patterns of its linear piece
-            rid = a["region_ids"]
-            nst = rid.shape[2] * 32
             # kept on the device: decoding 5e7 region ids per bag into 64 booleans each is a gather + shifts - seconds on the GPU,
             # minutes on the host (the oracle moves the masks to wherever it runs)
-            self.regions = {"rid": rid.view(B, H, nst // 32, J, 32).permute(0, 1, 3, 2, 4).reshape(B * H, J, nst).contiguous(),
-                            "pat": Fh.region_tables_view(a["tables"])["pat"].clone(),
-                            "w": [a[k].detach().double() for k in ("w1", "b1", "w2", "b2")], "vs": a["vs"].detach().double(),
-                            "gq": a["gq"].detach().double(), "device": rid.device}
+            self.regions = region_rows(a)
+            self.regions.update(rid=self.regions["rid"].contiguous(), pat=self.regions["pat"].clone(), device=a["region_ids"].device)
             return
         if a["masks2"] is None:           # table mode of the 16-bit core: the MLP runs on grid points only, no per-pair ReLU decisions
             return
@@ -228,6 +224,17 @@ class Decisions:
         if self.m2 is None:
             return None
         return self.decode(self.m1, i0, i1, device), self.decode(self.m2, i0, i1, device)
+
+
+def region_rows(attn_entry):
+    """The region ids of a DECISION_TAP entry of the region kernels, in the form region_decisions reads: 'rid' [(B H), J, nst] rows (from the
+    per-tile storage [B, H, nst / 32, J, 32]) and 'pat', the tables' ReLU patterns, with the fp64 weights and positions of the call."""
+    a = attn_entry
+    rid = a["region_ids"]
+    B, H, J, nst = a["B"], a["heads"], a["J"], rid.shape[2] * 32
+    return {"rid": rid.view(B, H, nst // 32, J, 32).permute(0, 1, 3, 2, 4).reshape(B * H, J, nst),
+            "pat": smml.functional.region_tables_view(a["tables"])["pat"], "w": [a[k].detach().double() for k in ("w1", "b1", "w2", "b2")],
+            "vs": a["vs"].detach().double(), "gq": a["gq"].detach().double()}
 
 
 def region_decisions(r, i0, i1, device="cpu"):
@@ -256,11 +263,7 @@ def decisions_of(attn_entry, device):
     Fh = smml.functional
     B, N, J, G, H = a["B"], a["N"], a["J"], a["groups"], a["heads"]
     if a.get("region_ids") is not None:
-        rid = a["region_ids"]
-        nst = rid.shape[2] * 32
-        r = {"rid": rid.view(B, H, nst // 32, J, 32).permute(0, 1, 3, 2, 4).reshape(B * H, J, nst), "pat": Fh.region_tables_view(a["tables"])["pat"],
-             "w": [a[k].detach().double() for k in ("w1", "b1", "w2", "b2")], "vs": a["vs"].detach().double(), "gq": a["gq"].detach().double()}
-        return region_decisions(r, 0, N, device)
+        return region_decisions(region_rows(a), 0, N, device)
     m1 = Decisions.decode(Fh.relu1_masks(a["vs"], a["gq"], a["w1"], a["b1"], B=B, N=N, J=J, groups=G, log_distance=a.get("log_distance", True)), 0, N, device)
     m2 = Decisions.decode(Fh.relu_masks_rows(a["masks2"])[:, ::H // G].reshape(B * G, J, 2, -1), 0, N, device)
     return m1, m2

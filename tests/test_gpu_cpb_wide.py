@@ -9,6 +9,8 @@ core for a bias MLP of width W = 64 / 128, i.e. DeformCrossAttention2D / 1D at d
   * the 2-D module at dim = 512 and the 1-D module at dim = 256 against the oracle in fp32 / fp64 with the decisions imposed;
   * the sampler backward at 64 channels per group against torch's grid_sample in fp64;
   * a hipGraph capture of a training step at dim = 256."""
+import contextlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -35,18 +37,13 @@ def _problem(gen, B, N, J, H, G, W, PD):
 
 def _run(t, cuda, wo, H, G, p_drop=0.0, seed=3, tap=False, log_distance=True, **kw):
     dev = {n: x.to(cuda).requires_grad_(n != "gq") for n, x in t.items()}
-    if tap:
-        Fh.DECISION_TAP = tapped = []
-    try:
+    with (decision_tap() if tap else contextlib.nullcontext()) as tapped:
         out = Fh.deform_attention(*(dev[n] for n in NAMES), heads=H, groups=G, scale=0.125, dropout_p=p_drop, dropout_seed=seed,
                                   log_distance=log_distance, **kw)
-    finally:
-        if tap:
-            Fh.DECISION_TAP = None
     (out * wo).sum().backward()
     torch.cuda.synchronize()
     res = {n: dev[n].grad.detach().clone() for n in NAMES if n != "gq"} | {"out": out.detach().clone()}
-    return (res, tapped) if tap else res
+    return (res, tapped.entries) if tap else res
 
 
 def _reference(r, H, G, scale, keep, keep_scale, masks, raw):
@@ -198,13 +195,11 @@ def test_module_dim256_against_the_reference_golden(cuda):
     mod, params, x1, x2, w_out, w_vg = dim256_problem(cuda)
     mod.load_state_dict(params)
     mod = mod.to(cuda).eval()
-    Fh.DECISION_TAP = tapped = []
-    try:
+    with decision_tap() as tap:
         out, vgrid = mod(x1, x2, return_vgrid=True)
-    finally:
-        Fh.DECISION_TAP = None
+    tapped = tap.entries
     assert [e for e in tapped if e["kind"] == "attn"][0].get("wide") == 64, "the module took the wrong path"
-    del tapped
+    del tapped, tap
     loss = (out * w_out).sum() + (vgrid * w_vg).sum()
     loss.backward()
     torch.cuda.synchronize()

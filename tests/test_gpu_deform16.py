@@ -63,8 +63,7 @@ def test_fused_core16_random_shapes(cuda, mode, tabfwd, monkeypatch):
         names = ("q", "k", "v", "vs", "gq", "w1", "b1", "w2", "b2", "w3", "b3")
         dev = {n: x.to(cuda).requires_grad_() for n, x in t.items()}
         seed = 170 + case
-        smml.functional.DECISION_TAP = tapped = []
-        try:
+        with decision_tap() as tap:
             # tabfwd: the forward's bias comes from the table (cpb_table='forward'), the backward recomputes layer 2 (always one bf16 term) and
             # exports the decisions it took - everything below then applies unchanged
             tkw = dict(cpb_table="forward", cpb_table_pmax=Fh.table_pmax(1.0, 1.2)) if tabfwd else {}
@@ -72,8 +71,7 @@ def test_fused_core16_random_shapes(cuda, mode, tabfwd, monkeypatch):
             # tests/test_gpu_regions.py and by the module-level tests below, which take it wherever it applies)
             out = Fh.deform_attention(*(dev[n] for n in names), heads=heads, groups=groups, scale=0.125, dropout_p=p_drop,
                                       dropout_seed=seed, compute_dtype=mode, cpb_regions=False, **tkw)
-        finally:
-            smml.functional.DECISION_TAP = None
+        tapped = tap.entries
         (out * wo.to(cuda)).sum().backward()
         keep = Fh.deform_attention_dropout_mask(B, N, J, heads, p_drop, seed, cuda) if p_drop else None
         a = tapped[0]

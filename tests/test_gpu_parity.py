@@ -573,12 +573,10 @@ def test_fused_core_random_shapes(cuda):
         wo = rn(B, N, 512)
         dev = {n: x.to(cuda).requires_grad_() for n, x in t.items()}
         seed = 17 + case
-        smml.functional.DECISION_TAP = tapped = []
-        try:
+        with decision_tap() as tap:
             out = Fh.deform_attention(*(dev[n] for n in ("q", "k", "v", "vs", "gq", "w1", "b1", "w2", "b2", "w3", "b3")), heads=heads,
                                       groups=groups, scale=0.125, dropout_p=p_drop, dropout_seed=seed)
-        finally:
-            smml.functional.DECISION_TAP = None
+        tapped = tap.entries
         (out * wo.to(cuda)).sum().backward()
         keep = Fh.deform_attention_dropout_mask(B, N, J, heads, p_drop, seed, cuda) if p_drop else None
         # the ReLU decisions the kernels took (layer 1 exported, layer 2 as saved for the backward), imposed on both torch evaluations

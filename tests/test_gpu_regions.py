@@ -8,6 +8,8 @@ The position-bias MLP of models/DeformableAttention2D.py:129-152 is piecewise af
     reference's goldens) on the same inputs, and against plain torch in fp64 with the kernels' decisions imposed;
   * determinism and the capacity fallbacks.
 No new tolerance: the bounds are those of tests/test_gpu_parity.py."""
+import contextlib
+
 import pytest
 import torch
 
@@ -111,18 +113,13 @@ def _problem(gen, B, N, J, heads, wkind="random", vs_scale=1.2):
 
 def _run(t, cuda, wo, regions, p_drop=0.0, seed=3, heads=8, tap=False, compute_dtype=None):
     dev = {n: x.to(cuda).requires_grad_(n != "gq") for n, x in t.items()}
-    if tap:
-        Fh.DECISION_TAP = tapped = []
-    try:
+    with (helpers.decision_tap() if tap else contextlib.nullcontext()) as tapped:
         out = Fh.deform_attention(*(dev[n] for n in NAMES), heads=heads, groups=heads, scale=0.125, dropout_p=p_drop, dropout_seed=seed,
                                   cpb_regions=regions, compute_dtype=compute_dtype)
-    finally:
-        if tap:
-            Fh.DECISION_TAP = None
     (out * wo).sum().backward()
     torch.cuda.synchronize()
     res = {n: dev[n].grad.detach().clone() for n in NAMES if n != "gq"} | {"out": out.detach().clone()}
-    return (res, tapped) if tap else res
+    return (res, tapped.entries) if tap else res
 
 
 @pytest.mark.parametrize("wkind,B,N,J,p_drop", [("random", 2, 700, 150, 0.1), ("bench", 1, 2500, 144, 0.0), ("star", 1, 333, 70, 0.0),

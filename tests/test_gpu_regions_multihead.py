@@ -6,6 +6,8 @@ MLP share layers 1 and 2, hence the regions and the lookup; only (a, c) differs 
     decisions against an fp64 evaluation, and equal region ids for the heads of a group;
   * the entry points: bit-identical to the one-output entry points at H == G, the global-memory regions, run-to-run identity and NaN
     propagation; the 16-bit modes against the 16-bit per-pair core; a hipGraph capture of a training step."""
+import contextlib
+
 import pytest
 import torch
 
@@ -31,18 +33,13 @@ def _problem(gen, B, N, J, heads, groups, vs_scale=1.2):
 
 def _run(t, cuda, wo, heads, groups, mh, p_drop=0.0, seed=3, tap=False, compute_dtype=None, regions=None):
     dev = {n: x.to(cuda).requires_grad_(n != "gq") for n, x in t.items()}
-    if tap:
-        Fh.DECISION_TAP = tapped = []
-    try:
+    with (helpers.decision_tap() if tap else contextlib.nullcontext()) as tapped:
         out = Fh.deform_attention(*(dev[n] for n in NAMES), heads=heads, groups=groups, scale=0.125, dropout_p=p_drop, dropout_seed=seed,
                                   cpb_regions=regions, cpb_regions_multi_head=mh, compute_dtype=compute_dtype)
-    finally:
-        if tap:
-            Fh.DECISION_TAP = None
     (out * wo).sum().backward()
     torch.cuda.synchronize()
     res = {n: dev[n].grad.detach().clone() for n in NAMES if n != "gq"} | {"out": out.detach().clone()}
-    return (res, tapped) if tap else res
+    return (res, tapped.entries) if tap else res
 
 
 def _first_head_of_each_group(entry):
@@ -66,11 +63,9 @@ def _module_step(mod, x1, x2, wo, train):
     mod.zero_grad(set_to_none=True)
     xa, xb = x1.clone().requires_grad_(), x2.clone().requires_grad_()
     torch.manual_seed(99)                                  # the dropout seed (drawn from torch's default generator)
-    Fh.DECISION_TAP = tapped = []
-    try:
+    with helpers.decision_tap() as tap:
         out = mod(xa, xb)
-    finally:
-        Fh.DECISION_TAP = None
+    tapped = tap.entries
     (out * wo).sum().backward()
     torch.cuda.synchronize()
     res = {"out": out.detach().clone(), "x1": xa.grad.detach().clone(), "x2": xb.grad.detach().clone()}
@@ -156,11 +151,9 @@ def test_module_against_the_reference_golden(cuda):
         mod, params, x1, x2, w_out, w_vg = g4_problem(cuda, cpb_regions_multi_head=mh)
         mod.load_state_dict(params)
         mod = mod.to(cuda).eval()
-        Fh.DECISION_TAP = tapped = []
-        try:
+        with helpers.decision_tap() as tap:
             out, vgrid = mod(x1, x2, return_vgrid=True)
-        finally:
-            Fh.DECISION_TAP = None
+        tapped = tap.entries
         assert ([e for e in tapped if e["kind"] == "attn"][0].get("region_ids") is not None) == mh, "the module took the wrong path"
         loss = (out * w_out).sum() + (vgrid * w_vg).sum()
         loss.backward()

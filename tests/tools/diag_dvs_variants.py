@@ -26,7 +26,7 @@ def tap_dvs(fn):
     def ab(ctx, dout):
         r = orig(ctx, dout); cap["cpb"] = r[3].detach().clone(); return r
     fn.backward = staticmethod(ab)
-tap_dvs(Fh._DeformAttnPair); tap_dvs(Fh._DeformAttnRegion)
+tap_dvs(Fh._DeformAttnMLP)
 enc, logits, _, omic_t, vg = net.pathomic_net_tumor(x_path.to(cuda), net.omic_net_tumor(x_omic=x_o.to(cuda))[0])
 (enc * w_enc.to(cuda)).sum().backward()
 tot = (cap["sampler"] + cap["cpb"]).cpu().double()
