@@ -597,6 +597,31 @@ int smml_attn16_bwd_f32(const float* q, const float* k, const float* v, const fl
                         const float* lse2, float* dq, float* dk, float* dv, void* workspace, size_t workspace_bytes, int BH, int Lq,
                         int Lk, int D, float scale, int use_fp16, int heads_merged, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Attention pooling of ABMIL (models/mil.py:66-75: the second attention layer, transpose, softmax over the bag, bmm with the raw features):
+ *   s[b, n] = h[b, n, :] . w2 + b2      out[b, :] = sum_n softmax_n(s[b, :])[n] x[b, n, :]      lse[b] = log sum_n exp(s[b, n])
+ * with h = tanh(x W1^T + b1) formed by smml_gemm_f32 (act 2).  One streaming pass over x and h with an online softmax: the bag's rows are cut
+ * into splits, each split leaves one partial (max, sum, accumulator [L]) in the workspace and a second kernel merges a bag's partials in
+ * ascending split order - no float atomics, one form, deterministic by construction.
+ *   x [B, N, L]   h [B, N, D]   w2 [D]   b2 [1] (in device memory, like w2)   s [B, N]   out [B, L]   lse [B];
+ *   any N >= 1, L a multiple of 256 up to 1024, D a multiple of 64 up
+ *   to 256 (anything else is an error); x, out and the workspace 16-byte aligned.
+ * splits: rows are cut into ceil(N / ceil(N / splits)) splits; 0 = chosen by the library (about 1024 workgroups over the B bags, no split
+ * under 48 rows).  The workspace functions take the same value.
+ * Backward, for dout [B, L] and the saved s, lse: t[b, n] = dout . x[b, n, :], p = exp(s - lse) / sum_n exp(s - lse) (the sum is re-formed:
+ * lse carries a rounding of |lse| 2^-24), c[b] = sum_n p t (= dout . out; formed from the row dots and kept in fp64 up to t - c, so that sum_n ds
+ * cancels to the rounding of its terms), ds = p (t - c); dh [B, N, D] = ds w2 (tanh_grad = 0: the gradient of h) or ds w2 (1 - h^2) (tanh_grad = 1: the gradient of
+ * the hidden layer's pre-activation, from which dW1 and db1 follow by smml_gemm_f32 and smml_colsum_f32), dw2 [D] = sum ds h and
+ * db2 [1] = sum ds, all overwritten; the row dots and the workgroups' dw2 / db2 partials go to the workspace, the partials are added in a
+ * fixed order.  No gradient of x is formed. */
+size_t smml_attn_pool_fwd_workspace_bytes(int B, int N, int L, int splits);
+int smml_attn_pool_fwd_f32(const float* x, const float* h, const float* w2, const float* b2, float* s, float* out, float* lse, void* workspace,
+                           size_t workspace_bytes, int B, int N, int L, int D, int splits, void* stream);
+size_t smml_attn_pool_bwd_workspace_bytes(int B, int N, int D, int splits);
+int smml_attn_pool_bwd_f32(const float* x, const float* h, const float* w2, const float* s, const float* lse, const float* dout, float* dh,
+                           float* dw2, float* db2, void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits,
+                           int tanh_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,8 +41,9 @@ class deterministic:
     value on exit, also when the block raises.  Every autograd Function reads the switch in its FORWARD and keeps the choice: its backward
     is deterministic as well, even when it runs after the block has ended.
 
-    Covered: the fp32-grade and 16-bit deform paths (DeformPathomicNet, both attn_dim values), BatchLoss and the co-attention
-    MultiheadAttention.  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
+    Covered: the fp32-grade and 16-bit deform paths (DeformPathomicNet, both attn_dim values), BatchLoss, the co-attention
+    MultiheadAttention and ABMIL (the attention-pooling kernels have a single form that is deterministic by construction - per-split
+    partials merged in a fixed order - and the switch only selects the fixed-order reductions of the hidden layer's gradients).  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
     bf16-storage GEMM with a split reduction, the depthwise-convolution weight gradients of the Nystrom block and of PPEG - raises
     RuntimeError under the switch; there is no silent fall-back.
 
@@ -352,6 +353,104 @@ class _DualLinearRelu(torch.autograd.Function):
 def dual_linear_relu(x, w0, b0, w1, b1):
     """(relu(x w0^T + b0), relu(x w1^T + b1)) for two heads of equal shape over one input."""
     return _DualLinearRelu.apply(x, w0, b0, w1, b1)
+
+
+# ------------------------------------------------------------------------------------------------
+# attention pooling of ABMIL (models/mil.py:66-75, csrc/attn_pool.hip): M[b] = sum_n softmax_n(h[b, n] . w2 + b2) x[b, n] - one streaming
+# pass over the bag with an online softmax, per-split partials merged in a fixed order
+# ------------------------------------------------------------------------------------------------
+POOL_MAX_L, POOL_MAX_D = 1024, 256
+
+
+def _pool_check(x, h, w2, b2):
+    """Shapes the pooling kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if x.dim() != 3 or h.dim() != 3 or tuple(h.shape[:2]) != tuple(x.shape[:2]):
+        raise ValueError(f"attention_pool: need x [B, N, L] and h [B, N, D] over the same bag, got {tuple(x.shape)} and {tuple(h.shape)}")
+    B, N, L = x.shape
+    D = h.shape[-1]
+    if N < 1 or B < 1:
+        raise ValueError(f"attention_pool: empty bag ({tuple(x.shape)})")
+    if L % 256 or not 0 < L <= POOL_MAX_L:
+        raise ValueError(f"attention_pool: the feature width L must be a multiple of 256 up to {POOL_MAX_L}, got {L}")
+    if D % 64 or not 0 < D <= POOL_MAX_D:
+        raise ValueError(f"attention_pool: the hidden width D must be a multiple of 64 up to {POOL_MAX_D}, got {D}")
+    if w2.numel() != D or b2.numel() != 1:
+        raise ValueError(f"attention_pool: one attention map (K = 1) - w2 must hold D = {D} values and b2 one, got {tuple(w2.shape)} and "
+                         f"{tuple(b2.shape)}")
+    return B, N, L, D
+
+
+class _AttnPool(torch.autograd.Function):
+    """hidden = False: h is an ordinary input and receives dh = ds w2.  hidden = True: h = tanh(x w1^T + b1) was formed outside the graph;
+    the backward kernel writes the pre-activation gradient ds w2 (1 - h^2) in the same pass and dw1 / db1 come from it exactly as
+    _Linear.backward forms them - no elementwise pass over a [B, N, D] tensor."""
+
+    @staticmethod
+    def forward(ctx, x, h, w2, b2, w1, b1, splits, scores_out):
+        B, N, L, D = _pool_check(x, h, w2, b2)
+        ctx.w2_shape, ctx.b2_shape = w2.shape, b2.shape
+        x = _c(x); h = _c(h); w2 = _c(w2).reshape(D); b2 = _c(b2).reshape(1)
+        ctx.det = DETERMINISTIC          # the pooling kernels have one form; the choice goes to the two reductions of the hidden layer's gradients
+        ctx.hidden = w1 is not None
+        ctx.splits = int(splits or 0)
+        Lb = capi.lib()
+        s = torch.empty(B, N, device=x.device, dtype=torch.float32)
+        M = torch.empty(B, L, device=x.device, dtype=torch.float32)
+        lse = torch.empty(B, device=x.device, dtype=torch.float32)
+        wsb = Lb.smml_attn_pool_fwd_workspace_bytes(B, N, L, ctx.splits)
+        ws = _scratch(wsb, x.device)
+        capi.check(Lb.smml_attn_pool_fwd_f32(capi.fptr(x), capi.fptr(h), capi.fptr(w2), capi.fptr(b2), capi.fptr(s), capi.fptr(M), capi.fptr(lse),
+                                             capi.fptr(ws), wsb, B, N, L, D, ctx.splits, capi.stream()), "attn_pool_fwd")
+        if scores_out is not None:
+            scores_out[:] = [s, lse]
+        ctx.save_for_backward(x, h, w2, s, lse)      # M is not needed: the backward forms dM . M from its own row dots (csrc/attn_pool.hip)
+        return M
+
+    @staticmethod
+    def backward(ctx, dM):
+        x, h, w2, s, lse = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("attention_pool: the pooled input is a bag of features (no gradient path is built)")
+        B, N, L = x.shape
+        D = h.shape[-1]
+        dM = _c(dM)
+        Lb = capi.lib()
+        dh = torch.empty_like(h)
+        dw2 = torch.empty(D, device=x.device, dtype=torch.float32)
+        db2 = torch.empty(1, device=x.device, dtype=torch.float32)
+        wsb = Lb.smml_attn_pool_bwd_workspace_bytes(B, N, D, ctx.splits)
+        ws = _scratch(wsb, x.device)
+        capi.check(Lb.smml_attn_pool_bwd_f32(capi.fptr(x), capi.fptr(h), capi.fptr(w2), capi.fptr(s), capi.fptr(lse), capi.fptr(dM),
+                                             capi.fptr(dh), capi.fptr(dw2), capi.fptr(db2), capi.fptr(ws), wsb, B, N, L, D, ctx.splits,
+                                             1 if ctx.hidden else 0, capi.stream()), "attn_pool_bwd")
+        dw1 = db1 = None
+        if ctx.hidden:
+            R = B * N
+            if ctx.needs_input_grad[4]:
+                dw1 = torch.empty(D, L, device=x.device, dtype=torch.float32) if ctx.det else _ZEROS.zeros((D, L), x.device)
+                _gemm(dh, x, dw1, M=D, N=L, K=R, sam=1, sak=D, sbk=L, sbn=1, ldc=L, splitk=_splitk_for(D, L, R), det=ctx.det)
+            if ctx.needs_input_grad[5]:
+                db1 = colsum(dh.reshape(1, R, D), det=ctx.det)[0]
+            dh = None
+        return None, dh, dw2.view(ctx.w2_shape), db2.view(ctx.b2_shape), dw1, db1, None, None
+
+
+def attention_pool(x, h, w2, b2, *, hidden=None, splits=None, scores_out=None):
+    """M [B, L] = sum_n softmax_n(h[b, n, :] . w2 + b2) x[b, n, :] for a bag x [B, N, L] and its hidden features h [B, N, D] (one attention
+    map: w2 holds D values, b2 one).  L a multiple of 256 up to 1024, D a multiple of 64 up to 256, any N >= 1; other shapes raise
+    ValueError.  x is a bag of features: it receives no gradient (x.requires_grad makes the backward raise RuntimeError).
+
+    hidden = (w1, b1): h is tanh(x w1^T + b1) formed WITHOUT autograd (linear(x, w1, b1, act=ACT_TANH) on detached operands or under
+    no_grad); the gradients of w1 and b1 are then produced here, from the pre-activation gradient the backward kernel writes in its one pass.
+    Without it h is an ordinary differentiable input.
+    splits: how many pieces a bag's rows are cut into (None: chosen by the library so that B x splits fills the chip); the result is a
+    function of the inputs and this number alone.  scores_out: a list that receives [s [B, N], lse [B]], the raw scores and their
+    log-sum-exp - softmax = exp(s - lse[:, None])."""
+    _pool_check(x, h, w2, b2)
+    w1, b1 = hidden if hidden is not None else (None, None)
+    if hidden is not None and h.requires_grad:
+        raise ValueError("attention_pool: with hidden = (w1, b1) h must be formed outside the autograd graph (its gradient is folded into dw1 / db1)")
+    return _AttnPool.apply(x, h, w2, b2, w1, b1, splits, scores_out)
 
 
 # ------------------------------------------------------------------------------------------------

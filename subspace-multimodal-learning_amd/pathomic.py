@@ -3,7 +3,7 @@
   MaxNet            models/model.py:142-187   omic SNN encoder (4 x Linear+ELU+AlphaDropout, ReLU, classifier)
   DeformPathomicNet models/model.py:440-544   two omic encoders + two DeformCrossTransMIL branches over the same
                                               bag, concat fusion, three classifiers; 7-tuple output
-  define_net        models/model.py:49-79     (mode 'deformpathomic' only)
+  define_net        models/model.py:49-79     (modes 'deformpathomic', 'path' = ABMIL of mil.py, 'omic' = MaxNet)
 
 Same constructor arguments (an `args` namespace with the keys of config/config_mine.yaml), forward kwargs,
 return tuple and parameter names.  fusion_type 'concat' (the shipped default, config_mine.yaml:17) and 'pofusion'
@@ -19,6 +19,7 @@ from torch.nn import Parameter
 from . import functional as Fh
 from .deform_cross_trans_mil import DeformCrossTransMIL
 from .fusion import define_bifusion
+from .mil import ABMIL
 
 
 def init_max_weights(module):
@@ -144,8 +145,13 @@ class DeformPathomicNet(nn.Module):
 
 
 def define_net(args):
-    """mode 'deformpathomic' of models/model.py:49-79 (init_net with init_type 'max' / 'none' leaves the
-    constructor's initialisation in place, utils/utils.py:222-240)."""
+    """Modes 'deformpathomic', 'path' (ABMIL, models/mil.py:34-82) and 'omic' (a bare MaxNet) of models/model.py:49-79 (init_net with
+    init_type 'max' / 'none' leaves the constructor's initialisation in place, utils/utils.py:222-240)."""
+    if args.mode == "path":
+        return ABMIL(args)
+    if args.mode == "omic":
+        return MaxNet(input_dim=args.input_size_omic, omic_dim=args.omic_dim, return_grad=args.return_grad, dropout_rate=args.dropout_rate,
+                      label_dim=args.label_dim, init_max=True if args.init_type == "max" else False)
     if args.mode != "deformpathomic":
         raise NotImplementedError(f"model [{args.mode}] is not part of the accelerated path")
     return DeformPathomicNet(args=args)
