@@ -43,7 +43,8 @@ int smml_event_elapsed_ms(void* start, void* stop, float* ms);
  *   C[b0,b1](m,n) (+)= act(alpha * sum_k A[b0,b1](m,k) B[b0,b1](k,n) + bias) + beta * residual
  * A(m,k) at A + b0*sa0 + b1*sa1 + m*sam + k*sak;  B(k,n) at B + b0*sb0 + b1*sb1 + k*sbk + n*sbn;
  * C(m,n) at C + b0*sc0 + b1*sc1 + m*ldc + n;  residual shares C's batch offsets with row stride ldr.
- * bias_mode 0 none | 1 bias[n] | 2 bias[(m / rows_per_bias) * bias_ld + n];  act 0 none | 1 relu | 2 tanh.
+ * bias_mode 0 none | 1 bias[n] | 2 bias[(m / rows_per_bias) * bias_ld + n];  act 0 none | 1 relu | 2 tanh |
+ * 3 sigmoid | 4 tanh on output columns [0, N / 2) and sigmoid on [N / 2, N) (N even: the two gates of a gated attention head in one product); act 3 / 4 always run the exact-fp32 kernels, whatever smml_gemm_set_mode says.
  * splitk > 1 or accumulate != 0: products are atomically added into C (caller zeroes C or keeps a running
  * sum there; no act / residual); batch strides of 0 on C fold a batch dimension into one output.
  * Replaces nn.Linear / 1x1 nn.Conv sites of the path: models/DeformCrossTransMIL.py:35-37,83,93-95,
@@ -605,7 +606,7 @@ int smml_attn16_bwd_f32(const float* q, const float* k, const float* v, const fl
  * ascending split order - no float atomics, one form, deterministic by construction.
  *   x [B, N, L]   h [B, N, D]   w2 [D]   b2 [1] (in device memory, like w2)   s [B, N]   out [B, L]   lse [B];
  *   any N >= 1, L a multiple of 256 up to 1024, D a multiple of 64 up
- *   to 256 (anything else is an error); x, out and the workspace 16-byte aligned.
+ *   to 256 (anything else is an error); x, out, dout and the workspaces 16-byte aligned.
  * splits: rows are cut into ceil(N / ceil(N / splits)) splits; 0 = chosen by the library (about 1024 workgroups over the B bags, no split
  * under 48 rows).  The workspace functions take the same value.
  * Backward, for dout [B, L] and the saved s, lse: t[b, n] = dout . x[b, n, :], p = exp(s - lse) / sum_n exp(s - lse) (the sum is re-formed:
@@ -621,6 +622,22 @@ size_t smml_attn_pool_bwd_workspace_bytes(int B, int N, int D, int splits);
 int smml_attn_pool_bwd_f32(const float* x, const float* h, const float* w2, const float* s, const float* lse, const float* dout, float* dh,
                            float* dw2, float* db2, void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits,
                            int tanh_grad, void* stream);
+
+/* The gated form (GatedABMIL, models/mil.py:102-152; the attention head of CLAM and of MCAT's Attn_Net_Gated):
+ *   s[b, n] = sum_d w[d] hv[b, n, d] hu[b, n, d] + b      with hv = tanh(x Wv^T + bv), hu = sigmoid(x Wu^T + bu)
+ * and everything after the score - online softmax, partials, merge, row dots, fixed-order reductions - as above.  The two hidden tensors are
+ * ONE buffer h2 [B, N, 2 D]: columns [0, D) hold hv and columns [D, 2 D) hold hu, as smml_gemm_f32 writes them with act 4 from the stacked
+ * weight [Wv; Wu].  D is the width of ONE half (a multiple of 64 up to 256); w [D], b [1]; the other shapes, the alignment rules, `splits`
+ * and the workspaces are those of the plain entry points: size them with smml_attn_pool_fwd_workspace_bytes(B, N, L, splits) and
+ * smml_attn_pool_bwd_workspace_bytes(B, N, D, splits).
+ * Backward, with ds as above and g = ds w[d]: dh2 [B, N, 2 D] holds g hu | g hv (act_grad = 0: the gradient of h2) or
+ * g hu (1 - hv^2) | g hv hu (1 - hu) (act_grad = 1: the gradient of the stacked pre-activation, from which d[Wv; Wu] and d[bv; bu] follow by
+ * one smml_gemm_f32 and one smml_colsum_f32), dw [D] = sum ds hv hu, db [1] = sum ds, all overwritten. */
+int smml_attn_pool_gated_fwd_f32(const float* x, const float* h2, const float* w, const float* b, float* s, float* out, float* lse,
+                                 void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits, void* stream);
+int smml_attn_pool_gated_bwd_f32(const float* x, const float* h2, const float* w, const float* s, const float* lse, const float* dout,
+                                 float* dh2, float* dw, float* db, void* workspace, size_t workspace_bytes, int B, int N, int L, int D,
+                                 int splits, int act_grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@
 //   backward  two streaming kernels on the same grid, one wave per row: the row dots t_n = dM . x_n (x, four rows in flight per wave), then
 //             ds_n = softmax_n (t_n - c) with c = sum_n softmax_n t_n, dH_n = ds_n w2 (.) (1 - H_n^2) (H, eight rows in flight) and the
 //             per-workgroup partials of dw2 / db2, which a third kernel sums in a fixed order.
+//   gated     GatedABMIL (models/mil.py:134-140): the score is sum_d w_d tanh(.)_d sigmoid(.)_d + b, the two hidden tensors are the halves of
+//             one buffer h2 [B, N, 2 D].  The forward and the second backward kernel are templated on GATED; merge, row dots and the final
+//             reduction are shared.
 // Every sum has one owner and a fixed order: no float atomics, the results are a function of the inputs and the split count alone.
 #include "smml_common.h"
 
@@ -49,6 +52,8 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
 
 // x [B, N, L], h [B, N, D], w2 [D], b2 [1] -> s [B, N], pacc [B, S, L], pml [B, S, 2]; split sp of bag b owns rows [sp rps, min(N, (sp + 1) rps))
+// GATED: h is h2 [B, N, 2 D], tanh units in columns [0, D) and sigmoid units in [D, 2 D) of one contiguous row; s_n = sum_d w_d hv_nd hu_nd + b
+template <bool GATED>
 __global__ __launch_bounds__(AP_THREADS) void attn_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ h,
                                                                    const float* __restrict__ w2, const float* __restrict__ b2p, float* __restrict__ s,
                                                                    float* __restrict__ pacc, float* __restrict__ pml, const int N, const int L,
@@ -61,7 +66,8 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_fwd_kernel(const float* 
   // every load is unconditional (straight-line code: the loads of a tile are issued back to back): a row past the split's end, a column past
   // L and a hidden panel past D re-read an address that is in range, and meet a weight of zero or are never stored
   const float* xb = x + (size_t)b * N * L + (col ? 4 * tid : 0);
-  const float* hb = h + (size_t)b * N * D + lane;
+  const int HS = GATED ? 2 * D : D;        // row stride of h
+  const float* hb = h + (size_t)b * N * HS + lane;
   __shared__ float sS[2][AP_TILE];       // the tile's scores; two buffers: a wave may fill the next tile's while another still reads this one's
 
   float w2r[4];
@@ -79,7 +85,16 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_fwd_kernel(const float* 
     for (int i = 0; i < 4; ++i) {
       const int row = min(t0 + wave + 4 * i, r1 - 1);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) hv[i][j] = hb[(size_t)row * D + (j < dj ? j * 64 : 0)];      // w2r[j] = 0 for j >= dj
+      for (int j = 0; j < 4; ++j) hv[i][j] = hb[(size_t)row * HS + (j < dj ? j * 64 : 0)];      // w2r[j] = 0 for j >= dj
+    }
+    float hu[GATED ? 4 : 1][4];              // the sigmoid half of the same rows: same clamps, D columns further (D + j 64 + lane < 2 D)
+    if constexpr (GATED) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = min(t0 + wave + 4 * i, r1 - 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hu[i][j] = hb[(size_t)row * HS + D + (j < dj ? j * 64 : 0)];
+      }
     }
     float4 xr[AP_TILE];
 #pragma unroll
@@ -88,7 +103,7 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_fwd_kernel(const float* 
     for (int i = 0; i < 4; ++i) {
       float d = 0.f;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) d = fmaf(hv[i][j], w2r[j], d);
+      for (int j = 0; j < 4; ++j) d = fmaf(GATED ? hv[i][j] * hu[i][j] : hv[i][j], w2r[j], d);
       d = wave_sum(d) + b2;
       if (lane == 0) sS[buf][wave + 4 * i] = (t0 + wave + 4 * i < r1) ? d : -INFINITY;     // a row past the end weighs exp(-inf) = 0
     }
@@ -215,6 +230,9 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_rowdot_kernel(const 
 }
 
 // saved h, s, lse and the row dots t -> dh [B, N, D] (times 1 - h^2 if tanh_grad) and part [B S, D + 64]
+// GATED: h is h2 [B, N, 2 D] = (hv | hu) and dh has its shape.  With g = ds w_d: tanh_grad writes the pre-activation gradients
+// g hu (1 - hv^2) | g hv hu (1 - hu), otherwise the gradients of h2 itself, g hu | g hv; dw_d = sum_n ds hv hu
+template <bool GATED>
 __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(const float* __restrict__ h, const float* __restrict__ w2,
                                                                    const float* __restrict__ s, const float* __restrict__ lse,
                                                                    const float* __restrict__ t, const double* __restrict__ zc,
@@ -224,8 +242,9 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(const float* 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r0 = sp * rps, r1 = r0 + min(rps, N - r0);
   const int dj = D >> 6;
-  const float* hb = h + (size_t)b * N * D + lane;           // loads are unconditional, as in the forward kernel
-  float* dhb = dh + (size_t)b * N * D + lane;
+  const int HS = GATED ? 2 * D : D;                          // row stride of h and dh
+  const float* hb = h + (size_t)b * N * HS + lane;          // loads are unconditional, as in the forward kernel
+  float* dhb = dh + (size_t)b * N * HS + lane;
   const float* sb = s + (size_t)b * N;
   const float* tb = t + (size_t)b * N;
 
@@ -259,9 +278,18 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(const float* 
     for (int i = 0; i < 8; ++i) {
       const size_t ri = (size_t)min(row + i, r1 - 1);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) hv[i][j] = hb[ri * D + (j < dj ? j * 64 : 0)];
+      for (int j = 0; j < 4; ++j) hv[i][j] = hb[ri * HS + (j < dj ? j * 64 : 0)];
       sv[i] = sb[ri];
       tv[i] = tb[ri];
+    }
+    float hu[GATED ? 8 : 1][4];              // the sigmoid half: same clamps, D columns further
+    if constexpr (GATED) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const size_t ri = (size_t)min(row + i, r1 - 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hu[i][j] = hb[ri * HS + D + (j < dj ? j * 64 : 0)];
+      }
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -271,10 +299,21 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(const float* 
       for (int j = 0; j < 4; ++j) {
         if (j < dj) {
           const float hh = hv[i][j];
-          float o = ds * w2r[j];
-          if (tanh_grad) o *= fmaf(-hh, hh, 1.f);
-          if (ok) dhb[(size_t)(row + i) * D + j * 64] = o;
-          dw[j] = fmaf(ds, hh, dw[j]);
+          if constexpr (GATED) {
+            const float uu = hu[i][j], g = ds * w2r[j];
+            float ov = g * uu, ou = g * hh;
+            if (tanh_grad) { ov *= fmaf(-hh, hh, 1.f); ou *= uu * (1.f - uu); }
+            if (ok) {
+              dhb[(size_t)(row + i) * HS + j * 64] = ov;
+              dhb[(size_t)(row + i) * HS + D + j * 64] = ou;
+            }
+            dw[j] = fmaf(ds, hh * uu, dw[j]);
+          } else {
+            float o = ds * w2r[j];
+            if (tanh_grad) o *= fmaf(-hh, hh, 1.f);
+            if (ok) dhb[(size_t)(row + i) * D + j * 64] = o;
+            dw[j] = fmaf(ds, hh, dw[j]);
+          }
         }
       }
       db += ds;
@@ -337,6 +376,51 @@ bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; 
 // floats of the backward's row dots t [B, N], padded so that what follows them in the workspace stays 16-byte aligned
 size_t bwd_rowdot_floats(int B, int N) { return ((size_t)B * (size_t)N + 3) / 4 * 4; }
 
+// the plain and the gated entry points differ in the hidden tensor's row (D or 2 D floats) and in the kernel instantiation alone
+template <bool GATED>
+int pool_fwd(const char* fn, const float* x, const float* h, const float* w2, const float* b2, float* s, float* out, float* lse,
+             void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits, void* stream) {
+  SMML_REQUIRE(x && h && w2 && b2 && s && out && lse && workspace, "%s: null pointer", fn);
+  SMML_REQUIRE(pool_shape_ok(B, N, L, D), "%s: need L a multiple of 256 up to %d and D a multiple of 64 up to %d, N >= 1, "
+               "B <= 65535 (got B %d, N %d, L %d, D %d)", fn, AP_MAXL, AP_MAXD, B, N, L, D);
+  SMML_REQUIRE(aligned16(x) && aligned16(out) && aligned16(workspace), "%s: x, out and workspace must be 16-byte aligned", fn);
+  SMML_REQUIRE(workspace_bytes >= smml_attn_pool_fwd_workspace_bytes(B, N, L, splits), "%s: workspace too small", fn);
+  const int rps = pool_rows_per_split(B, N, splits), S = pool_splits(N, rps);
+  float* pacc = (float*)workspace;
+  float* pml = pacc + (size_t)B * S * L;
+  hipLaunchKernelGGL(attn_pool_fwd_kernel<GATED>, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, x, h, w2, b2, s, pacc,
+                     pml, N, L, D, rps);
+  SMML_LAUNCH_CHECK(fn);
+  hipLaunchKernelGGL(attn_pool_merge_kernel, dim3((unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, pacc, pml, out, lse, S, L);
+  SMML_LAUNCH_CHECK(fn);
+  return SMML_OK;
+}
+
+template <bool GATED>
+int pool_bwd(const char* fn, const float* x, const float* h, const float* w2, const float* s, const float* lse, const float* dout,
+             float* dh, float* dw2, float* db2, void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits,
+             int tanh_grad, void* stream) {
+  SMML_REQUIRE(x && h && w2 && s && lse && dout && dh && dw2 && db2 && workspace, "%s: null pointer", fn);
+  SMML_REQUIRE(pool_shape_ok(B, N, L, D), "%s: need L a multiple of 256 up to %d and D a multiple of 64 up to %d, N >= 1, "
+               "B <= 65535 (got B %d, N %d, L %d, D %d)", fn, AP_MAXL, AP_MAXD, B, N, L, D);
+  SMML_REQUIRE(aligned16(x) && aligned16(dout) && aligned16(workspace), "%s: x, dout and workspace must be 16-byte aligned", fn);
+  SMML_REQUIRE(workspace_bytes >= smml_attn_pool_bwd_workspace_bytes(B, N, D, splits), "%s: workspace too small", fn);
+  const int rps = pool_rows_per_split(B, N, splits), S = pool_splits(N, rps);
+  float* t = (float*)workspace;
+  double* zc = (double*)(t + bwd_rowdot_floats(B, N));
+  float* part = (float*)(zc + (size_t)B * S * 2);
+  hipLaunchKernelGGL(attn_pool_bwd_rowdot_kernel, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, x, dout, s, lse, t, zc,
+                     N, L, rps);
+  SMML_LAUNCH_CHECK(fn);
+  hipLaunchKernelGGL(attn_pool_bwd_kernel<GATED>, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, h, w2, s, lse, t, zc,
+                     dh, part, N, D, rps, tanh_grad);
+  SMML_LAUNCH_CHECK(fn);
+  hipLaunchKernelGGL(attn_pool_bwd_reduce_kernel, dim3((unsigned)(bwd_part_ld(D) / 64)), dim3(64 * AP_REDUCE_WAVES), 0, (hipStream_t)stream, part,
+                     (long long)B * S, D, dw2, db2);
+  SMML_LAUNCH_CHECK(fn);
+  return SMML_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -349,20 +433,12 @@ size_t smml_attn_pool_fwd_workspace_bytes(int B, int N, int L, int splits) {
 
 int smml_attn_pool_fwd_f32(const float* x, const float* h, const float* w2, const float* b2, float* s, float* out, float* lse, void* workspace,
                            size_t workspace_bytes, int B, int N, int L, int D, int splits, void* stream) {
-  SMML_REQUIRE(x && h && w2 && b2 && s && out && lse && workspace, "smml_attn_pool_fwd_f32: null pointer");
-  SMML_REQUIRE(pool_shape_ok(B, N, L, D), "smml_attn_pool_fwd_f32: need L a multiple of 256 up to %d and D a multiple of 64 up to %d, N >= 1, "
-               "B <= 65535 (got B %d, N %d, L %d, D %d)", AP_MAXL, AP_MAXD, B, N, L, D);
-  SMML_REQUIRE(aligned16(x) && aligned16(out) && aligned16(workspace), "smml_attn_pool_fwd_f32: x, out and workspace must be 16-byte aligned");
-  SMML_REQUIRE(workspace_bytes >= smml_attn_pool_fwd_workspace_bytes(B, N, L, splits), "smml_attn_pool_fwd_f32: workspace too small");
-  const int rps = pool_rows_per_split(B, N, splits), S = pool_splits(N, rps);
-  float* pacc = (float*)workspace;
-  float* pml = pacc + (size_t)B * S * L;
-  hipLaunchKernelGGL(attn_pool_fwd_kernel, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, x, h, w2, b2, s, pacc, pml,
-                     N, L, D, rps);
-  SMML_LAUNCH_CHECK("smml_attn_pool_fwd_f32");
-  hipLaunchKernelGGL(attn_pool_merge_kernel, dim3((unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, pacc, pml, out, lse, S, L);
-  SMML_LAUNCH_CHECK("smml_attn_pool_fwd_f32/merge");
-  return SMML_OK;
+  return pool_fwd<false>("smml_attn_pool_fwd_f32", x, h, w2, b2, s, out, lse, workspace, workspace_bytes, B, N, L, D, splits, stream);
+}
+
+int smml_attn_pool_gated_fwd_f32(const float* x, const float* h2, const float* w, const float* b, float* s, float* out, float* lse,
+                                 void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits, void* stream) {
+  return pool_fwd<true>("smml_attn_pool_gated_fwd_f32", x, h2, w, b, s, out, lse, workspace, workspace_bytes, B, N, L, D, splits, stream);
 }
 
 size_t smml_attn_pool_bwd_workspace_bytes(int B, int N, int D, int splits) {
@@ -374,25 +450,15 @@ size_t smml_attn_pool_bwd_workspace_bytes(int B, int N, int D, int splits) {
 int smml_attn_pool_bwd_f32(const float* x, const float* h, const float* w2, const float* s, const float* lse, const float* dout, float* dh,
                            float* dw2, float* db2, void* workspace, size_t workspace_bytes, int B, int N, int L, int D, int splits,
                            int tanh_grad, void* stream) {
-  SMML_REQUIRE(x && h && w2 && s && lse && dout && dh && dw2 && db2 && workspace, "smml_attn_pool_bwd_f32: null pointer");
-  SMML_REQUIRE(pool_shape_ok(B, N, L, D), "smml_attn_pool_bwd_f32: need L a multiple of 256 up to %d and D a multiple of 64 up to %d, N >= 1, "
-               "B <= 65535 (got B %d, N %d, L %d, D %d)", AP_MAXL, AP_MAXD, B, N, L, D);
-  SMML_REQUIRE(aligned16(x) && aligned16(dout), "smml_attn_pool_bwd_f32: x and dout must be 16-byte aligned");
-  SMML_REQUIRE(workspace_bytes >= smml_attn_pool_bwd_workspace_bytes(B, N, D, splits), "smml_attn_pool_bwd_f32: workspace too small");
-  const int rps = pool_rows_per_split(B, N, splits), S = pool_splits(N, rps);
-  float* t = (float*)workspace;
-  double* zc = (double*)(t + bwd_rowdot_floats(B, N));
-  float* part = (float*)(zc + (size_t)B * S * 2);
-  hipLaunchKernelGGL(attn_pool_bwd_rowdot_kernel, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, x, dout, s, lse, t, zc,
-                     N, L, rps);
-  SMML_LAUNCH_CHECK("smml_attn_pool_bwd_f32/rowdot");
-  hipLaunchKernelGGL(attn_pool_bwd_kernel, dim3((unsigned)S, (unsigned)B), dim3(AP_THREADS), 0, (hipStream_t)stream, h, w2, s, lse, t, zc, dh,
-                     part, N, D, rps, tanh_grad);
-  SMML_LAUNCH_CHECK("smml_attn_pool_bwd_f32");
-  hipLaunchKernelGGL(attn_pool_bwd_reduce_kernel, dim3((unsigned)(bwd_part_ld(D) / 64)), dim3(64 * AP_REDUCE_WAVES), 0, (hipStream_t)stream, part,
-                     (long long)B * S, D, dw2, db2);
-  SMML_LAUNCH_CHECK("smml_attn_pool_bwd_f32/reduce");
-  return SMML_OK;
+  return pool_bwd<false>("smml_attn_pool_bwd_f32", x, h, w2, s, lse, dout, dh, dw2, db2, workspace, workspace_bytes, B, N, L, D, splits,
+                         tanh_grad, stream);
+}
+
+int smml_attn_pool_gated_bwd_f32(const float* x, const float* h2, const float* w, const float* s, const float* lse, const float* dout,
+                                 float* dh2, float* dw, float* db, void* workspace, size_t workspace_bytes, int B, int N, int L, int D,
+                                 int splits, int act_grad, void* stream) {
+  return pool_bwd<true>("smml_attn_pool_gated_bwd_f32", x, h2, w, s, lse, dout, dh2, dw, db, workspace, workspace_bytes, B, N, L, D, splits,
+                        act_grad, stream);
 }
 
 }  // extern "C"

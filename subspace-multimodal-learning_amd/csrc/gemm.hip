@@ -31,12 +31,22 @@ struct GemmArgs {
   long long scs; // C stride of a split-K slice: 0 (the slices share one C) or, in the partial-output mode of smml_gemm_f32_det, M * N
 };
 
-__device__ __forceinline__ float apply_act(float v, int act) {
+// GATE: the kernels of the sigmoid epilogues (act 3: sigmoid; act 4: tanh on output columns [0, N / 2), sigmoid on [N / 2, N)) are
+// instantiations of their own, launched for those two codes alone.  The epilogues are unrolled per element: with the two cases in every
+// kernel, each product kernel grew by up to 40 % of its instructions, the act 0 / 1 / 2 launches paid for it and their code - and with it
+// the rounding of their results - changed.  GATE = false is the code these kernels always had.
+template <bool GATE>
+__device__ __forceinline__ float apply_act(float v, int act, int n, int N) {
   if (act == 1) return fmaxf(v, 0.f);
   if (act == 2) return tanhf(v);
+  if constexpr (GATE) {
+    if (act == 3 || (act == 4 && 2 * n >= N)) return 1.f / (1.f + expf(-v));      // v -> -inf: 1 / inf = 0
+    if (act == 4) return tanhf(v);
+  }
   return v;
 }
 
+template <bool GATE>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   __shared__ float As[BK][LDA];
   __shared__ float Bs[BK][LDB];
@@ -121,7 +131,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
         atomicAdd(&C[m * g.ldc + n], v);
       } else {
         if (bias) v += (g.bias_mode == 2) ? bias[(m / g.rows_per_bias) * g.bias_ld + n] : bias[n];
-        v = apply_act(v, g.act);
+        v = apply_act<GATE>(v, g.act, n, g.N);
         if (res) v = fmaf(g.beta, res[m * g.ldr + n], v);
         C[m * g.ldc + n] = v;
       }
@@ -138,7 +148,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 // Requirements (checked on the host): K % 16 == 0, 16-byte aligned operands with the unit stride on k or on
 // the row index and all other strides multiples of 4 elements.
 // ------------------------------------------------------------------------------------------------
-template <int BN_, bool A_KC, bool B_KC, int FBM = 128>
+template <int BN_, bool A_KC, bool B_KC, int FBM = 128, bool GATE = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_fast_kernel(GemmArgs g) {
   constexpr int FBK = 16, NI = BN_ / 64, MI = FBM / 64;      // MI x NI 32x32 blocks per wave; FBM = 64: the small-problem tile
   constexpr int NA = FBM / 64;                               // float4 of A per thread per K-tile
@@ -302,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_fast_kernel(GemmArgs g) {
           const int m = mb + acc_row(r, hf);
           float v = g.alpha * acc[mi][ni][r];
           if (bias) v += (g.bias_mode == 2) ? bias[(m / g.rows_per_bias) * g.bias_ld + n] : bias[n];
-          v = apply_act(v, g.act);
+          v = apply_act<GATE>(v, g.act, n, g.N);
           C[(long long)m * g.ldc + n] = fmaf(g.beta, rv[r], v);
         }
       }
@@ -324,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_fast_kernel(GemmArgs g) {
           atomicAdd(&C[m * g.ldc + n], v);
         } else {
           if (bias) v += (g.bias_mode == 2) ? bias[(m / g.rows_per_bias) * g.bias_ld + n] : bias[n];
-          v = apply_act(v, g.act);
+          v = apply_act<GATE>(v, g.act, n, g.N);
           if (res) v = fmaf(g.beta, res[m * g.ldr + n], v);
           C[m * g.ldc + n] = v;
         }
@@ -529,7 +539,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(GemmArgs g) {
           const int m = mb + acc_row(r, hf);
           float v = g.alpha * acc[mi][ni][r];
           if (bias) v += (g.bias_mode == 2) ? bias[(m / g.rows_per_bias) * g.bias_ld + n] : bias[n];
-          v = apply_act(v, g.act);
+          v = apply_act<false>(v, g.act, n, g.N);
           C[(long long)m * g.ldc + n] = fmaf(g.beta, rv[r], v);
         }
       }
@@ -551,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(GemmArgs g) {
           atomicAdd(&C[m * g.ldc + n], v);
         } else {
           if (bias) v += (g.bias_mode == 2) ? bias[(m / g.rows_per_bias) * g.bias_ld + n] : bias[n];
-          v = apply_act(v, g.act);
+          v = apply_act<false>(v, g.act, n, g.N);
           if (res) v = fmaf(g.beta, res[m * g.ldr + n], v);
           C[m * g.ldc + n] = v;
         }
@@ -612,7 +622,8 @@ static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C
   SMML_REQUIRE(!((atomic || scs) && (act != 0 || residual)), "%s: split-K / accumulate excludes activation/residual", fn);
   SMML_REQUIRE(bias_mode >= 0 && bias_mode <= 2, "%s: bad bias_mode %d", fn, bias_mode);
   SMML_REQUIRE(bias_mode != 2 || rows_per_bias > 0, "%s: rows_per_bias must be positive", fn);
-  SMML_REQUIRE(act >= 0 && act <= 2, "%s: bad activation %d", fn, act);
+  SMML_REQUIRE(act >= 0 && act <= 4, "%s: bad activation %d", fn, act);
+  SMML_REQUIRE(act != 4 || N % 2 == 0, "%s: activation 4 (tanh | sigmoid halves) needs an even N, got %d", fn, N);
   const long long gz = (long long)nb0 * nb1 * splitk;
   const long long gy = (N + BN - 1) / BN, gx = (M + BM - 1) / BM;
   const int swap_xy = gy > 65535;
@@ -631,6 +642,7 @@ static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C
   const bool a_ok = al16(A) && al4(sa0) && al4(sa1) && ((a_kc && al4(sam)) || (a_mc && al4(sak)));
   const bool b_ok = al16(B) && al4(sb0) && al4(sb1) && ((b_kc && al4(sbn)) || (b_nc && al4(sbk)));
   const bool k_ok = (!a_kc && !b_kc) || (K % 4) == 0;
+  const bool gate = act >= 3;            // the sigmoid epilogues live in the exact-fp32 kernels only, whatever the precision mode
   if (a_ok && b_ok && k_ok && !g_force_generic) {
     // 128-wide column tiles only when they still fill the chip a few times over (2 workgroups per CU resident)
     const int bn = (N > 64 && gx * ((N + 127) / 128) * gz >= 1024) ? 128 : 64;
@@ -650,13 +662,15 @@ static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C
     // TF on the Nystrom qkv product, 173 vs 124 TF at 4096^3) - but inside the training step, A/B on one box
     // (SMML_GEMM_MODE=1 vs automatic with that wider rule), the step is not faster (17.2 / 17.5 vs 17.6 / 17.5 ms) and
     // the errors against the oracle grow 2x.  So the automatic choice keeps it for large square-ish products only.
-    const bool bf3 = (g_mode == 2) || (g_mode == 0 && K >= 2048 && M >= 1024 && N >= 1024);
-    const bool bf1 = (g_mode == 3), f1 = (g_mode == 4);
+    const bool bf3_mode = (g_mode == 2) || (g_mode == 0 && K >= 2048 && M >= 1024 && N >= 1024);
+    const bool bf3 = !gate && bf3_mode;
+    const bool bf1 = !gate && (g_mode == 3), f1 = !gate && (g_mode == 4);
 #define SMML_FAST(BNV, AK, BK2)                                                                   \
   do {                                                                                            \
     if (f1) hipLaunchKernelGGL((gemm_bf3_kernel<BNV, AK, BK2, 1, 128, true>), grid, dim3(256), 0, st, g); \
     else if (bf1) hipLaunchKernelGGL((gemm_bf3_kernel<BNV, AK, BK2, 1>), grid, dim3(256), 0, st, g);   \
     else if (bf3) hipLaunchKernelGGL((gemm_bf3_kernel<BNV, AK, BK2>), grid, dim3(256), 0, st, g); \
+    else if (gate) hipLaunchKernelGGL((gemm_f32_fast_kernel<BNV, AK, BK2, 128, true>), grid, dim3(256), 0, st, g); \
     else hipLaunchKernelGGL((gemm_f32_fast_kernel<BNV, AK, BK2>), grid, dim3(256), 0, st, g);     \
   } while (0)
 #define SMML_SMALL(AK, BK2)                                                                          \
@@ -664,6 +678,7 @@ static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C
     if (f1) hipLaunchKernelGGL((gemm_bf3_kernel<64, AK, BK2, 1, 64, true>), grid, dim3(256), 0, st, g);   \
     else if (bf1) hipLaunchKernelGGL((gemm_bf3_kernel<64, AK, BK2, 1, 64>), grid, dim3(256), 0, st, g);   \
     else if (bf3) hipLaunchKernelGGL((gemm_bf3_kernel<64, AK, BK2, 3, 64>), grid, dim3(256), 0, st, g); \
+    else if (gate) hipLaunchKernelGGL((gemm_f32_fast_kernel<64, AK, BK2, 64, true>), grid, dim3(256), 0, st, g); \
     else hipLaunchKernelGGL((gemm_f32_fast_kernel<64, AK, BK2, 64>), grid, dim3(256), 0, st, g);     \
   } while (0)
     if (small) {
@@ -682,7 +697,8 @@ static int gemm_f32_run(const char* fn, const float* A, const float* B, float* C
     return SMML_OK;
   }
   dim3 grid((unsigned)(swap_xy ? gy : gx), (unsigned)(swap_xy ? gx : gy), (unsigned)gz);
-  hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
+  if (gate) hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g);
+  else hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, g);
   SMML_LAUNCH_CHECK("smml_gemm_f32");
   return SMML_OK;
 }

@@ -16,6 +16,8 @@ import torch
 from . import _capi as capi
 
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+ACT_SIGMOID = 3
+ACT_TANH_SIGMOID = 4         # tanh on output columns [0, N / 2), sigmoid on [N / 2, N): the two gates of a gated attention head in one product
 
 
 # ------------------------------------------------------------------------------------------------
@@ -285,6 +287,11 @@ class _Linear(torch.autograd.Function):
                                                     capi.stream()), "relu_bwd")
         elif ctx.act == ACT_TANH:
             dpre = dy * (1.0 - y * y)          # only ever [B, C]-sized (Pooler)
+        elif ctx.act == ACT_SIGMOID:
+            dpre = dy * (y * (1.0 - y))
+        elif ctx.act == ACT_TANH_SIGMOID:          # the gated pooling forms these in its own backward kernel (attention_pool_gated)
+            yv, yu = y[..., :N // 2], y[..., N // 2:]
+            dpre = dy * torch.cat((1.0 - yv * yv, yu * (1.0 - yu)), dim=-1)
         else:
             dpre = dy
         dx = dw = db = None
@@ -306,7 +313,11 @@ class _Linear(torch.autograd.Function):
 def linear(x, weight, bias=None, act: int = ACT_NONE, rows_per_bias: int = 1, residual=None, prec: int = 0):
     """act(x W^T + bias) (+ residual).  prec: GEMM precision mode of the forward and backward products (0 automatic / exact
     fp32, 2 three-term split bf16, 3 single-term bf16 operands - the 16-bit compute mode, 4 single-term fp16 operands in the forward
-    product and bf16 ones in the two gradient products - the fp16 compute modes)."""
+    product and bf16 ones in the two gradient products - the fp16 compute modes).
+    act: ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID or ACT_TANH_SIGMOID (tanh on the first half of the output columns, sigmoid on the second;
+    an odd number of columns raises ValueError)."""
+    if act == ACT_TANH_SIGMOID and weight.shape[0] % 2:
+        raise ValueError(f"linear: ACT_TANH_SIGMOID splits the output columns in halves, got an odd N = {weight.shape[0]}")
     return _Linear.apply(x, weight, bias, act, rows_per_bias, residual, prec)
 
 
@@ -451,6 +462,106 @@ def attention_pool(x, h, w2, b2, *, hidden=None, splits=None, scores_out=None):
     if hidden is not None and h.requires_grad:
         raise ValueError("attention_pool: with hidden = (w1, b1) h must be formed outside the autograd graph (its gradient is folded into dw1 / db1)")
     return _AttnPool.apply(x, h, w2, b2, w1, b1, splits, scores_out)
+
+
+# ------------------------------------------------------------------------------------------------
+# gated attention pooling (GatedABMIL, models/mil.py:102-152; csrc/attn_pool.hip): the score is sum_d w_d tanh(.)_d sigmoid(.)_d + b, the two
+# hidden tensors are the halves of ONE buffer h2 [B, N, 2 D] - the output of one GEMM over x with the stacked weight [Wv; Wu]
+# ------------------------------------------------------------------------------------------------
+def _pool_gated_check(x, h2, w, b):
+    """Shapes the gated pooling kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if x.dim() != 3 or h2.dim() != 3 or tuple(h2.shape[:2]) != tuple(x.shape[:2]):
+        raise ValueError(f"attention_pool_gated: need x [B, N, L] and h2 [B, N, 2 D] over the same bag, got {tuple(x.shape)} and "
+                         f"{tuple(h2.shape)}")
+    B, N, L = x.shape
+    D2 = h2.shape[-1]
+    if N < 1 or B < 1:
+        raise ValueError(f"attention_pool_gated: empty bag ({tuple(x.shape)})")
+    if L % 256 or not 0 < L <= POOL_MAX_L:
+        raise ValueError(f"attention_pool_gated: the feature width L must be a multiple of 256 up to {POOL_MAX_L}, got {L}")
+    if D2 % 128 or not 0 < D2 <= 2 * POOL_MAX_D:
+        raise ValueError(f"attention_pool_gated: h2 holds the tanh and the sigmoid half side by side - its width 2 D must be a multiple of "
+                         f"128 up to {2 * POOL_MAX_D}, got {D2}")
+    D = D2 // 2
+    if w.numel() != D or b.numel() != 1:
+        raise ValueError(f"attention_pool_gated: one attention map (K = 1) - w must hold D = {D} values and b one, got {tuple(w.shape)} and "
+                         f"{tuple(b.shape)}")
+    return B, N, L, D
+
+
+class _AttnPoolGated(torch.autograd.Function):
+    """hidden = False: h2 is an ordinary input and receives dh2 = (g hu | g hv), g = ds w.  hidden = True: h2 = (tanh(x Wv^T + bv) |
+    sigmoid(x Wu^T + bu)) was formed outside the graph; the backward kernel writes the gradient of the stacked pre-activation in the same
+    pass, one GEMM over x yields d[Wv; Wu] and one column sum d[bv; bu] - both split by views."""
+
+    @staticmethod
+    def forward(ctx, x, h2, w, b, wv, bv, wu, bu, splits, scores_out):
+        B, N, L, D = _pool_gated_check(x, h2, w, b)
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        x = _c(x); h2 = _c(h2); w = _c(w).reshape(D); b = _c(b).reshape(1)
+        ctx.det = DETERMINISTIC          # the pooling kernels have one form; the choice goes to the two reductions of the hidden layer's gradients
+        ctx.hidden = wv is not None
+        ctx.splits = int(splits or 0)
+        Lb = capi.lib()
+        s = torch.empty(B, N, device=x.device, dtype=torch.float32)
+        M = torch.empty(B, L, device=x.device, dtype=torch.float32)
+        lse = torch.empty(B, device=x.device, dtype=torch.float32)
+        wsb = Lb.smml_attn_pool_fwd_workspace_bytes(B, N, L, ctx.splits)
+        ws = _scratch(wsb, x.device)
+        capi.check(Lb.smml_attn_pool_gated_fwd_f32(capi.fptr(x), capi.fptr(h2), capi.fptr(w), capi.fptr(b), capi.fptr(s), capi.fptr(M),
+                                                   capi.fptr(lse), capi.fptr(ws), wsb, B, N, L, D, ctx.splits, capi.stream()),
+                   "attn_pool_gated_fwd")
+        if scores_out is not None:
+            scores_out[:] = [s, lse]
+        ctx.save_for_backward(x, h2, w, s, lse)
+        return M
+
+    @staticmethod
+    def backward(ctx, dM):
+        x, h2, w, s, lse = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("attention_pool_gated: the pooled input is a bag of features (no gradient path is built)")
+        B, N, L = x.shape
+        D = h2.shape[-1] // 2
+        dM = _c(dM)
+        Lb = capi.lib()
+        dh2 = torch.empty_like(h2)
+        dw = torch.empty(D, device=x.device, dtype=torch.float32)
+        db = torch.empty(1, device=x.device, dtype=torch.float32)
+        wsb = Lb.smml_attn_pool_bwd_workspace_bytes(B, N, D, ctx.splits)
+        ws = _scratch(wsb, x.device)
+        capi.check(Lb.smml_attn_pool_gated_bwd_f32(capi.fptr(x), capi.fptr(h2), capi.fptr(w), capi.fptr(s), capi.fptr(lse), capi.fptr(dM),
+                                                   capi.fptr(dh2), capi.fptr(dw), capi.fptr(db), capi.fptr(ws), wsb, B, N, L, D, ctx.splits,
+                                                   1 if ctx.hidden else 0, capi.stream()), "attn_pool_gated_bwd")
+        dwv = dbv = dwu = dbu = None
+        if ctx.hidden:
+            R = B * N
+            if ctx.needs_input_grad[4] or ctx.needs_input_grad[6]:
+                dwvu = torch.empty(2 * D, L, device=x.device, dtype=torch.float32) if ctx.det else _ZEROS.zeros((2 * D, L), x.device)
+                _gemm(dh2, x, dwvu, M=2 * D, N=L, K=R, sam=1, sak=2 * D, sbk=L, sbn=1, ldc=L, splitk=_splitk_for(2 * D, L, R), det=ctx.det)
+                dwv, dwu = dwvu[:D], dwvu[D:]
+            if ctx.needs_input_grad[5] or ctx.needs_input_grad[7]:
+                dbvu = colsum(dh2.reshape(1, R, 2 * D), det=ctx.det)[0]
+                dbv, dbu = dbvu[:D], dbvu[D:]
+            dh2 = None
+        return None, dh2, dw.view(ctx.w_shape), db.view(ctx.b_shape), dwv, dbv, dwu, dbu, None, None
+
+
+def attention_pool_gated(x, h2, w, b, *, hidden=None, splits=None, scores_out=None):
+    """M [B, L] = sum_n softmax_n(sum_d w_d hv[b, n, d] hu[b, n, d] + b) x[b, n, :] for a bag x [B, N, L] and its two gates in ONE tensor
+    h2 [B, N, 2 D]: hv = h2[..., :D] (the tanh units) and hu = h2[..., D:] (the sigmoid units); one attention map: w holds D values, b one.
+    L a multiple of 256 up to 1024, D a multiple of 64 up to 256, any N >= 1; other shapes raise ValueError.  x is a bag of features: it
+    receives no gradient (x.requires_grad makes the backward raise RuntimeError).
+
+    hidden = (Wv, bv, Wu, bu): h2 is linear(x, cat(Wv, Wu), cat(bv, bu), act=ACT_TANH_SIGMOID) formed WITHOUT autograd (detached operands or
+    no_grad); the four gradients are then produced here, from the pre-activation gradient the backward kernel writes in its one pass.
+    Without it h2 is an ordinary differentiable input.  splits, scores_out: as in attention_pool."""
+    _pool_gated_check(x, h2, w, b)
+    wv, bv, wu, bu = hidden if hidden is not None else (None, None, None, None)
+    if hidden is not None and h2.requires_grad:
+        raise ValueError("attention_pool_gated: with hidden = (Wv, bv, Wu, bu) h2 must be formed outside the autograd graph (its gradient is "
+                         "folded into the four parameter gradients)")
+    return _AttnPoolGated.apply(x, h2, w, b, wv, bv, wu, bu, splits, scores_out)
 
 
 # ------------------------------------------------------------------------------------------------

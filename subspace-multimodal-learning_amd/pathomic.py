@@ -146,7 +146,8 @@ class DeformPathomicNet(nn.Module):
 
 def define_net(args):
     """Modes 'deformpathomic', 'path' (ABMIL, models/mil.py:34-82) and 'omic' (a bare MaxNet) of models/model.py:49-79 (init_net with
-    init_type 'max' / 'none' leaves the constructor's initialisation in place, utils/utils.py:222-240)."""
+    init_type 'max' / 'none' leaves the constructor's initialisation in place, utils/utils.py:222-240).  The extension key `abmil_gated`
+    is read by ABMIL itself: mode 'path' with it set gives the gated attention network (mil.py)."""
     if args.mode == "path":
         return ABMIL(args)
     if args.mode == "omic":
