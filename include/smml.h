@@ -639,6 +639,37 @@ int smml_attn_pool_gated_bwd_f32(const float* x, const float* h2, const float* w
                                  float* dh2, float* dw, float* db, void* workspace, size_t workspace_bytes, int B, int N, int L, int D,
                                  int splits, int act_grad, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Few-query co-attention (models/MultiheadAttention.py with one head and L <= 8 queries over S keys: CMTA's G_in_P_Att, MCAT's coattn), the
+ * bag-sized core of the folded form.  With q^ = (query Wq^T + bq) scaling, u = q^ Wk and c = q^ . bk (formed by the caller, [B, L, E]-sized):
+ *   raw[b, l, s] = u[b, l, :] . x[b, s, :] + c[b, l]      z[b, l, :] = sum_s softmax_s(raw[b, l, :])[s] y[b, s, :]      lse[b, l] = log sum_s exp(raw)
+ * and the module's output is (z Wv^T + bv) Wo^T + bo.  One streaming pass over x (and y) with one online softmax per query; the bag's rows
+ * are cut into splits as for smml_attn_pool_*, one partial (m[L], l[L], acc[L, Ev]) per split, merged in ascending split order - no float
+ * atomics, one form, deterministic by construction.
+ *   u [B, L, Ek]   c [B, L]   z [B, L, Ev]   raw [B, L, S]   lse [B, L]   dense;
+ *   x [B, S, Ek], y [B, S, Ev]: unit column stride, rows *_row_stride and bags *_batch_stride floats apart (multiples of 4; a slice or a
+ *   sequence-first tensor is read in place).  y may BE x (same pointer, strides and width, as at every call site of the reference): the rows
+ *   are then read once.  key_padding_mask [B, S] bytes (non-zero: the key is masked, its raw score is -inf) or null.
+ *   L <= 8, Ek and Ev multiples of 64 up to 512, any S >= 1 (anything else is an error); u, x, y, z, dz, dx, dy and the workspaces 16-byte
+ *   aligned.  A bag whose keys are ALL masked gives NaN, as in the reference; that is not checked.
+ * splits: as for smml_attn_pool_fwd_f32 (0 = about 1024 workgroups over the B bags, no split under 64 rows).
+ * Backward, for dz [B, L, Ev], the saved raw, lse, z and optionally draw [B, L, S] (the gradient of the raw scores) and dlse [B, L] (either
+ * may be null): p = exp(raw - lse), t = dz . y_s, kappa = dz . z, ds = p (t - kappa + dlse) + draw (0 at masked keys);
+ *   du [B, L, Ek] = sum_s ds x_s   dc [B, L] = sum_s ds   dx [B, S, Ek] = sum_l ds u_l   dy [B, S, Ev] = sum_l p dz_l   all overwritten,
+ * dx and dy with strides of their own.  dx and dy may be null (nothing is formed for them); where y is x the one row dx + dy goes to dx and
+ * dy must be null.  The workgroups' du / dc partials go to the workspace and are added in ascending split order. */
+size_t smml_fewq_attn_fwd_workspace_bytes(int B, int L, int S, int Ev, int splits);
+int smml_fewq_attn_fwd_f32(const float* u, const float* c, const float* x, const float* y, const unsigned char* key_padding_mask, float* z,
+                           float* raw, float* lse, void* workspace, size_t workspace_bytes, int B, int L, int S, int Ek, int Ev,
+                           long long x_batch_stride, long long x_row_stride, long long y_batch_stride, long long y_row_stride, int splits,
+                           void* stream);
+size_t smml_fewq_attn_bwd_workspace_bytes(int B, int L, int S, int Ek, int splits);
+int smml_fewq_attn_bwd_f32(const float* u, const float* x, const float* y, const float* raw, const float* lse, const float* z, const float* dz,
+                           const float* draw, const float* dlse, float* du, float* dc, float* dx, float* dy, void* workspace,
+                           size_t workspace_bytes, int B, int L, int S, int Ek, int Ev, long long x_batch_stride, long long x_row_stride,
+                           long long y_batch_stride, long long y_row_stride, long long dx_batch_stride, long long dx_row_stride,
+                           long long dy_batch_stride, long long dy_row_stride, int splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,10 @@ Same constructor, forward signature, return tuple and parameter names (in_proj_w
 out_proj.weight/bias).  In-projections, Q K^T, softmax, P V and the out-projection run on the HIP kernels.
 Every constructor option of the reference's class runs - no caller in
 the reference uses them.  The reference's `torch.equal(query, key)` host sync (:126,130) only selects between
-algebraically identical in-projection paths and is not reproduced."""
+algebraically identical in-projection paths and is not reproduced.
+
+Extension, off by default: `fused_few_query = True` routes one-head calls with at most 8 queries (G_in_P_Att: 4 genomic queries over the
+bag) through the folded form on csrc/fewq_attn.hip - one streaming pass over the bag, no projected key / value tensors."""
 from __future__ import annotations
 
 import torch
@@ -51,6 +54,11 @@ class MultiheadAttention(nn.Module):
         else:
             self.bias_k = self.bias_v = None
         self.add_zero_attn = add_zero_attn
+        # extension (not in the reference): True sends calls that coattn_path() routes to 'fewq' - one head, at most 8 queries, no attn_mask,
+        # no bias_kv / zero_attn rows, dropout inactive - through the folded form on csrc/fewq_attn.hip: the bag is read once and no
+        # projected key / value tensor is formed.  Plain attributes, not parameters or buffers: the state_dict is unchanged.
+        self.fused_few_query = False
+        self.fewq_splits = None               # pieces a bag's rows are cut into on that path (None: the library chooses; tests force ragged ones)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -78,6 +86,10 @@ class MultiheadAttention(nn.Module):
         bq = bk = bv = None
         if self.in_proj_bias is not None:
             bq, bk, bv = self.in_proj_bias.chunk(3, dim=0)
+        if Fh.coattn_path(L=L, heads=h, Ek=key.shape[-1], Ev=value.shape[-1], attn_mask=attn_mask is not None,
+                          add_bias_kv=self.bias_k is not None, add_zero_attn=self.add_zero_attn,
+                          dropout_active=self.training and self.dropout > 0, fused=self.fused_few_query) == "fewq":
+            return self._forward_few_query(query, key, value, key_padding_mask, need_weights, need_raw, (wq, wk, wv), (bq, bk, bv), scaling)
 
         def heads_first(t, n):          # [B, n, E] -> [B, h, n, hd]
             return t.reshape(B, 1, n, E) if h == 1 else t.reshape(B, n, h, hd).permute(0, 2, 1, 3)
@@ -130,3 +142,22 @@ class MultiheadAttention(nn.Module):
                 return out, raw
             return out, attn.sum(dim=1) / h
         return out, None
+
+    def _forward_few_query(self, query, key, value, key_padding_mask, need_weights, need_raw, w, b, scaling):
+        """The folded form: raw = (q^ Wk) . x_s + q^ . bk and out = Wo (Wv z + bv) + bo with z = sum_s softmax(raw) y_s.  The bag-sized
+        work is the core of functional.few_query_attention; the [B, L, E]-sized products around it are GEMM launches inside the same
+        autograd node (functional.coattn_few_query).  Several heads would fold the same way, as h L queries that each read their own column
+        slice of Wk / Wv; only one head is wired."""
+        (wq, wk, wv), (bq, bk, bv) = w, b
+        B, S = query.shape[1], key.shape[0]
+        if key_padding_mask is not None and tuple(key_padding_mask.shape) != (B, S):
+            raise RuntimeError("key_padding_mask must be [batch, source length]")
+        out, raw, lse = Fh.coattn_few_query(query.transpose(0, 1), key.transpose(0, 1), value.transpose(0, 1), wq, bq, wk, bk, wv, bv,
+                                            self.out_proj.weight, self.out_proj.bias, scaling=scaling, key_padding_mask=key_padding_mask,
+                                            splits=self.fewq_splits)
+        out = out.transpose(0, 1)
+        if not need_weights:
+            return out, None
+        if need_raw:
+            return out, raw.unsqueeze(1)                                              # [B, 1, L, S], masked entries -inf
+        return out, torch.exp(raw - lse.unsqueeze(-1))                                # the softmax [B, L, S] (one head: the head average is itself)

@@ -45,7 +45,8 @@ class deterministic:
 
     Covered: the fp32-grade and 16-bit deform paths (DeformPathomicNet, both attn_dim values), BatchLoss, the co-attention
     MultiheadAttention and ABMIL (the attention-pooling kernels have a single form that is deterministic by construction - per-split
-    partials merged in a fixed order - and the switch only selects the fixed-order reductions of the hidden layer's gradients).  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
+    partials merged in a fixed order - and the switch only selects the fixed-order reductions of the hidden layer's gradients; the
+    few-query co-attention kernels are of the same kind, the switch selects the fixed-order forms of the weight gradients around them).  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
     bf16-storage GEMM with a split reduction, the depthwise-convolution weight gradients of the Nystrom block and of PPEG - raises
     RuntimeError under the switch; there is no silent fall-back.
 
@@ -562,6 +563,306 @@ def attention_pool_gated(x, h2, w, b, *, hidden=None, splits=None, scores_out=No
         raise ValueError("attention_pool_gated: with hidden = (Wv, bv, Wu, bu) h2 must be formed outside the autograd graph (its gradient is "
                          "folded into the four parameter gradients)")
     return _AttnPoolGated.apply(x, h2, w, b, wv, bv, wu, bu, splits, scores_out)
+
+
+# ------------------------------------------------------------------------------------------------
+# few-query co-attention (models/MultiheadAttention.py with one head and L <= 8 queries over a bag; csrc/fewq_attn.hip): with
+# q^ = (query Wq^T + bq) scaling, raw = u . x_s + c for u = q^ Wk, c = q^ . bk and the output is Wv z + bv for z = sum_s softmax(raw) y_s -
+# the key / value projections fold into [B, L, E]-sized products and the bag streams once through few_query_attention
+# ------------------------------------------------------------------------------------------------
+FEWQ_MAX_L, FEWQ_MAX_E = 8, 512
+
+
+def _fewq_width_ok(E: int) -> bool:
+    return 0 < E <= FEWQ_MAX_E and E % 64 == 0
+
+
+def coattn_why(*, L: int, heads: int, Ek: int, Ev: int, attn_mask: bool = False, add_bias_kv: bool = False, add_zero_attn: bool = False,
+               dropout_active: bool = False, fused: bool = True) -> Optional[str]:
+    """Why a MultiheadAttention call with L queries, `heads` heads and raw key / value widths Ek / Ev stays on the composed path (two
+    bag-sized projections, matmul4, softmax_rows, matmul4); None: it takes the few-query kernels.  No GPU work."""
+    if not fused:
+        return "fused_few_query is off (the default)"
+    if heads != 1:
+        return f"{heads} heads (the few-query kernels are one-head)"
+    if not 1 <= L <= FEWQ_MAX_L:
+        return f"{L} queries (at most {FEWQ_MAX_L})"
+    if attn_mask:
+        return "an attn_mask (only key_padding_mask is fused)"
+    if add_bias_kv:
+        return "add_bias_kv (a learned key / value row outside the bag)"
+    if add_zero_attn:
+        return "add_zero_attn (a zero key / value row outside the bag)"
+    if dropout_active:
+        return "active attention dropout"
+    if not _fewq_width_ok(Ek) or not _fewq_width_ok(Ev):
+        return f"key / value widths {Ek} / {Ev} (multiples of 64 up to {FEWQ_MAX_E})"
+    return None
+
+
+def coattn_path(**kw) -> str:
+    """'fewq' (the folded form on csrc/fewq_attn.hip) or 'composed' for a MultiheadAttention call: the arguments of coattn_why, which names
+    the reason for 'composed'."""
+    return "composed" if coattn_why(**kw) is not None else "fewq"
+
+
+def _fewq_check(u, c, x, y):
+    """Shapes the few-query kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if u.dim() != 3 or x.dim() != 3 or y.dim() != 3 or c.dim() != 2:
+        raise ValueError(f"few_query_attention: need u [B, L, Ek], c [B, L], x [B, S, Ek], y [B, S, Ev], got {tuple(u.shape)}, {tuple(c.shape)}, "
+                         f"{tuple(x.shape)}, {tuple(y.shape)}")
+    B, L, Ek = u.shape
+    S, Ev = x.shape[1], y.shape[2]
+    if tuple(c.shape) != (B, L) or tuple(x.shape) != (B, S, Ek) or tuple(y.shape[:2]) != (B, S):
+        raise ValueError(f"few_query_attention: u {tuple(u.shape)}, c {tuple(c.shape)}, x {tuple(x.shape)} and y {tuple(y.shape)} do not "
+                         "describe one problem")
+    if B < 1 or S < 1:
+        raise ValueError(f"few_query_attention: empty bag ({tuple(x.shape)})")
+    if not 1 <= L <= FEWQ_MAX_L:
+        raise ValueError(f"few_query_attention: at most {FEWQ_MAX_L} queries, got {L}")
+    if not _fewq_width_ok(Ek) or not _fewq_width_ok(Ev):
+        raise ValueError(f"few_query_attention: the key and value widths must be multiples of 64 up to {FEWQ_MAX_E}, got {Ek} and {Ev}")
+    return B, L, S, Ek, Ev
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """t [B, S, E] as the kernels read it in place: fp32, unit column stride, rows and bags a multiple of 4 floats apart, 16-byte aligned -
+    a slice of a longer bag or a sequence-first tensor's transpose qualifies; anything else is copied."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    B, S, E = t.shape
+    ok = (t.stride(2) == 1 and t.stride(1) >= E and t.stride(1) % 4 == 0 and (t.stride(0) % 4 == 0 or B == 1) and t.data_ptr() % 16 == 0)
+    return t if ok else t.contiguous()
+
+
+def _rows_ptr(t: Optional[torch.Tensor]):
+    if t is None:
+        return None
+    if not t.is_cuda or t.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"smml kernels need fp32 tensors on the current device (cuda:{torch.cuda.current_device()}), got {t.device}; "
+                           "this path has no CPU fallback")
+    return C_.c_void_p(t.data_ptr())
+
+
+def _bs(t: torch.Tensor) -> int:
+    return int(t.stride(0)) if t.shape[0] > 1 else 0
+
+
+def _grad_rows(t: torch.Tensor) -> torch.Tensor:
+    """An uninitialised gradient buffer for the rows t: t's own layout where that is dense (a sequence-first tensor gets its gradient
+    sequence-first, no copy on the way to .grad), contiguous otherwise."""
+    if t.transpose(0, 1).is_contiguous():
+        return torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=torch.float32)
+    return torch.empty(t.shape, device=t.device, dtype=torch.float32)
+
+
+def _fewq_fwd(u, c, x, yv, mask, splits: int):
+    """One launch of the forward core on checked operands (u, c dense; x, yv as _rows leaves them; yv is x: the values are the keys)."""
+    B, L, Ek = u.shape
+    S, Ev = x.shape[1], yv.shape[2]
+    Lb = capi.lib()
+    z = torch.empty(B, L, Ev, device=x.device, dtype=torch.float32)
+    raw = torch.empty(B, L, S, device=x.device, dtype=torch.float32)
+    lse = torch.empty(B, L, device=x.device, dtype=torch.float32)
+    wsb = Lb.smml_fewq_attn_fwd_workspace_bytes(B, L, S, Ev, splits)
+    ws = _scratch(wsb, x.device)
+    capi.check(Lb.smml_fewq_attn_fwd_f32(capi.fptr(u), capi.fptr(c), _rows_ptr(x), _rows_ptr(yv), capi.ptr(mask), capi.fptr(z), capi.fptr(raw),
+                                         capi.fptr(lse), capi.fptr(ws), wsb, B, L, S, Ek, Ev, _bs(x), x.stride(1), _bs(yv), yv.stride(1),
+                                         splits, capi.stream()), "fewq_attn_fwd")
+    return z, raw, lse
+
+
+def _fewq_bwd(u, x, y, raw, lse, z, dz, draw, dlse, want_dx: bool, want_dy: bool, splits: int):
+    """One launch of the backward core -> (du, dc, dx, dy); y = None: the values are the keys and dx holds dx + dy.  dz / draw / dlse may
+    be None (no gradient arrived for that output)."""
+    yv = x if y is None else y
+    B, L, Ek = u.shape
+    S, Ev = x.shape[1], yv.shape[2]
+    dz = _c(dz) if dz is not None else torch.zeros_like(z)
+    draw = _c(draw) if draw is not None else None
+    dlse = _c(dlse) if dlse is not None else None
+    Lb = capi.lib()
+    du = torch.empty_like(u)
+    dc = torch.empty(B, L, device=x.device, dtype=torch.float32)
+    dx = _grad_rows(x) if want_dx else None
+    dy = _grad_rows(yv) if y is not None and want_dy else None
+    wsb = Lb.smml_fewq_attn_bwd_workspace_bytes(B, L, S, Ek, splits)
+    ws = _scratch(wsb, x.device)
+    st = lambda t: (_bs(t), t.stride(1)) if t is not None else (0, 0)      # noqa: E731
+    capi.check(Lb.smml_fewq_attn_bwd_f32(capi.fptr(u), _rows_ptr(x), _rows_ptr(yv), capi.fptr(raw), capi.fptr(lse), capi.fptr(z), capi.fptr(dz),
+                                         capi.fptr(draw), capi.fptr(dlse), capi.fptr(du), capi.fptr(dc), _rows_ptr(dx), _rows_ptr(dy),
+                                         capi.fptr(ws), wsb, B, L, S, Ek, Ev, *st(x), *st(yv), *st(dx), *st(dy), splits, capi.stream()),
+               "fewq_attn_bwd")
+    return du, dc, dx, dy
+
+
+class _FewQueryAttention(torch.autograd.Function):
+    """y = None: the value rows ARE the key rows - one read in the forward, one read and one written gradient row (dx + dy) in the backward."""
+
+    @staticmethod
+    def forward(ctx, u, c, x, y, mask, splits):
+        B, L, S, Ek, Ev = _fewq_check(u, c, x, x if y is None else y)
+        ctx.set_materialize_grads(False)
+        u = _c(u); c = _c(c); x = _rows(x)
+        yv = x if y is None else _value_rows(x, y)
+        ctx.same = y is None
+        ctx.splits = int(splits or 0)
+        z, raw, lse = _fewq_fwd(u, c, x, yv, mask, ctx.splits)
+        ctx.save_for_backward(u, x, None if ctx.same else yv, raw, lse, z)
+        return z, raw, lse
+
+    @staticmethod
+    def backward(ctx, dz, draw, dlse):
+        u, x, y, raw, lse, z = ctx.saved_tensors
+        du, dc, dx, dy = _fewq_bwd(u, x, y, raw, lse, z, dz, draw, dlse, ctx.needs_input_grad[2],
+                                   ctx.needs_input_grad[3], ctx.splits)
+        return du, dc, dx, dy, None, None
+
+
+def _same_rows(x: torch.Tensor, y: Optional[torch.Tensor]) -> bool:
+    """y names x's rows AND the one gradient row dx + dy may go to x: the same tensor, two views of one base over the same memory (the two
+    `bag.transpose(1, 0)` of a co-attention call: the base receives the sum either way), or aliases of which neither requires a gradient.
+    A detached alias on one side (`mod(q, kv, kv.detach())`) is NOT the same rows: the side that requires a gradient gets its own part alone."""
+    if y is None or y is x:
+        return True
+    if y.data_ptr() != x.data_ptr() or y.shape != x.shape or y.stride() != x.stride() or y.dtype != x.dtype:
+        return False
+    if y._base is not None and y._base is x._base:
+        return True
+    return not x.requires_grad and not y.requires_grad
+
+
+def _value_rows(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """The value rows of the distinct form.  The C entry points read `y == x` (pointer and strides) as the one-row form; values that alias
+    the keys without being the same rows for autograd (_same_rows) are therefore copied - the price of a call no model makes."""
+    yv = _rows(y)
+    same_memory = yv.data_ptr() == x.data_ptr() and yv.shape == x.shape and yv.stride() == x.stride()
+    return yv.clone() if same_memory else yv
+
+
+def few_query_attention(u, c, x, y=None, *, key_padding_mask=None, splits=None):
+    """(z [B, L, Ev], raw [B, L, S], lse [B, L]) with raw[b, l, s] = u[b, l] . x[b, s] + c[b, l], z = sum_s softmax_s(raw) y[b, s] and
+    lse = log sum_s exp(raw), for L <= 8 queries u [B, L, Ek], c [B, L] over a bag of keys x [B, S, Ek] and values y [B, S, Ev] - one
+    streaming pass over the bag with an online softmax per query.  Ek and Ev multiples of 64 up to 512, any S >= 1; other shapes raise
+    ValueError before anything is launched.  x and y are read in place when their columns are contiguous (a slice of a longer bag, the
+    transpose of a sequence-first tensor).
+
+    y = None (or x itself, or another view of x's base over the same memory): the values are the keys - the bag is read once, and x
+    receives the ONE gradient row dx + dy.  A y that aliases x while only one of the two requires a gradient (x.detach()) is a distinct
+    value tensor: it is copied and each side gets its own part alone.
+    key_padding_mask [B, S] bool: masked keys get raw = -inf, weight 0 and a zero gradient row; a bag with every key masked gives NaN, as
+    the reference does (not checked: that would be a host sync).
+    All three outputs are differentiable; u, c, x and y receive gradients (x / y only where they require one - no buffer is written
+    otherwise).
+    splits: how many pieces a bag's rows are cut into (None: chosen by the library so that B x splits fills the chip); the result is a
+    function of the inputs and this number alone - the same under functional.deterministic()."""
+    same = _same_rows(x, y)
+    _fewq_check(u, c, x, x if same else y)
+    mask = None
+    if key_padding_mask is not None:
+        mask = key_padding_mask.to(torch.bool).contiguous().view(torch.uint8)
+        if tuple(mask.shape) != (x.shape[0], x.shape[1]):
+            raise ValueError(f"few_query_attention: key_padding_mask must be [B, S] = {(x.shape[0], x.shape[1])}, got {tuple(mask.shape)}")
+    return _FewQueryAttention.apply(u, c, x, None if same else y, mask, splits)
+
+
+def _lin(x2, w, b=None, alpha: float = 1.0):
+    """alpha x2 [R, K] w [N, K]^T (+ b) -> [R, N]"""
+    R, K = x2.shape
+    N = w.shape[0]
+    y = torch.empty(R, N, device=x2.device, dtype=torch.float32)
+    _gemm(x2, w, y, M=R, N=N, K=K, sam=K, sak=1, sbk=1, sbn=K, ldc=N, bias=b, bias_mode=0 if b is None else 1, bias_ld=N, alpha=alpha)
+    return y
+
+
+def _mat(x2, w, alpha: float = 1.0):
+    """alpha x2 [R, K] w [K, N] -> [R, N]"""
+    R, K = x2.shape
+    N = w.shape[1]
+    y = torch.empty(R, N, device=x2.device, dtype=torch.float32)
+    _gemm(x2, w, y, M=R, N=N, K=K, sam=K, sak=1, sbk=N, sbn=1, ldc=N, alpha=alpha)
+    return y
+
+
+def _wgrad(dy, x2, det: bool, alpha: float = 1.0):
+    """alpha dy [R, N]^T x2 [R, K] -> [N, K], the weight gradient of _lin as _Linear.backward forms it"""
+    R, N = dy.shape
+    K = x2.shape[1]
+    dw = torch.empty(N, K, device=dy.device, dtype=torch.float32) if det else _ZEROS.zeros((N, K), dy.device)
+    _gemm(dy, x2, dw, M=N, N=K, K=R, sam=1, sak=N, sbk=K, sbn=1, ldc=K, splitk=_splitk_for(N, K, R), alpha=alpha, det=det)
+    return dw
+
+
+class _CoattnFewQuery(torch.autograd.Function):
+    """The whole folded co-attention as ONE autograd node: the [B L, E]-sized products around the core are the same smml_gemm launches
+    linear / matmul4 would issue (q^ = q Wq^T + bq; u = s q^ Wk, c = s q^ . bk with the scaling s as the products' alpha; Wv z + bv; the
+    out-projection) and their gradients are formed as _Linear.backward forms them.  A chain of eight Functions computes the same values
+    with the same kernels; at L <= 8 it spent several times the kernels' time in the host's per-node bookkeeping (33 launches against
+    this node's 27: DESIGN.md 4c, profiles/coattn_fewq_kernel_stats.csv), which is what this node removes."""
+
+    @staticmethod
+    def forward(ctx, q, x, y, wq, bq, wk, bk, wv, bv, wo, bo, mask, splits, scaling):
+        B, L, E = q.shape
+        ctx.set_materialize_grads(False)
+        ctx.det = DETERMINISTIC
+        ctx.splits, ctx.scaling, ctx.same = int(splits or 0), float(scaling), y is None
+        ctx.shapes = tuple(None if b is None else b.shape for b in (bq, bk, bv, bo))
+        q2 = _c(q).reshape(B * L, E)
+        wq, wk, wv, wo = _c(wq), _c(wk), _c(wv), _c(wo)
+        bqc, bkc, bvc, boc = (None if b is None else _c(b).reshape(-1) for b in (bq, bk, bv, bo))
+        x = _rows(x)
+        yv = x if y is None else _value_rows(x, y)
+        qh = _lin(q2, wq, bqc)
+        u = _mat(qh, wk, alpha=ctx.scaling).view(B, L, -1)
+        c = _lin(qh, bkc.view(1, E), alpha=ctx.scaling).view(B, L) if bkc is not None else torch.zeros(B, L, device=q.device)
+        z, raw, lse = _fewq_fwd(u, c, x, yv, mask, ctx.splits)
+        o = _lin(z.view(B * L, -1), wv, bvc)
+        out = _lin(o, wo, boc).view(B, L, -1)
+        ctx.save_for_backward(q2, qh, u, x, None if ctx.same else yv, raw, lse, z, o, wq, wk, bkc, wv, wo)
+        return out, raw, lse
+
+    @staticmethod
+    def backward(ctx, dout, draw, dlse):
+        q2, qh, u, x, y, raw, lse, z, o, wq, wk, bk, wv, wo = ctx.saved_tensors
+        B, L, _ = u.shape
+        R, s, det = B * L, ctx.scaling, ctx.det
+        dout = (_c(dout) if dout is not None else torch.zeros(B, L, wo.shape[0], device=u.device)).reshape(R, -1)
+        col = lambda g, shape: None if shape is None else colsum(g.reshape(1, R, -1), det=det)[0].view(shape)      # noqa: E731
+        do = _mat(dout, wo)
+        dwo, dbo = _wgrad(dout, o, det), col(dout, ctx.shapes[3])
+        dz = _mat(do, wv).view(B, L, -1)
+        dwv, dbv = _wgrad(do, z.view(R, -1), det), col(do, ctx.shapes[2])
+        du, dc, dx, dy = _fewq_bwd(u, x, y, raw, lse, z, dz, draw, dlse, ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.splits)
+        du2, dc2 = du.view(R, -1), dc.view(R, 1)
+        dqh = _lin(du2, wk, alpha=s)                                        # s du Wk^T ...
+        dwk = _wgrad(qh, du2, det, alpha=s)
+        dbk = None
+        if bk is not None:
+            dqh.addcmul_(dc2, bk.view(1, -1), value=s)                      # ... + s dc bk^T, [B L, E]-sized
+            dbk = _wgrad(qh, dc2, det, alpha=s).view(ctx.shapes[1])
+        dq = _mat(dqh, wq).view(B, L, -1) if ctx.needs_input_grad[0] else None
+        dwq, dbq = _wgrad(dqh, q2, det), col(dqh, ctx.shapes[0])
+        return dq, dx, dy, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, None, None, None
+
+
+def coattn_few_query(q, x, y, wq, bq, wk, bk, wv, bv, wo, bo, *, scaling: float, key_padding_mask=None, splits=None):
+    """(out [B, L, E], raw [B, L, S], lse [B, L]) of one-head co-attention in the folded form, batch first: q [B, L, E] queries, x [B, S, Ek]
+    keys, y [B, S, Ev] values (None or x's rows: the values are the keys), Wq [E, E], Wk [E, Ek], Wv [E, Ev], Wo [E, E] and their biases
+    (any may be None).  The bag-sized work is few_query_attention's core; shapes, masks, `splits` and determinism as there.  All three
+    outputs and every input are differentiable."""
+    same = _same_rows(x, y)
+    if q.dim() != 3 or wk.dim() != 2 or wk.shape[0] != q.shape[-1] or wv.shape[0] != q.shape[-1]:
+        raise ValueError(f"coattn_few_query: need q [B, L, E], Wk [E, Ek], Wv [E, Ev], got {tuple(q.shape)}, {tuple(wk.shape)}, {tuple(wv.shape)}")
+    B, L, _ = q.shape
+    _fewq_check(torch.empty(B, L, wk.shape[1], device="meta"), torch.empty(B, L, device="meta"), x, x if same else y)
+    if wv.shape[1] != (x if same else y).shape[-1]:
+        raise ValueError(f"coattn_few_query: Wv {tuple(wv.shape)} does not take values of width {(x if same else y).shape[-1]}")
+    mask = None
+    if key_padding_mask is not None:
+        mask = key_padding_mask.to(torch.bool).contiguous().view(torch.uint8)
+        if tuple(mask.shape) != (x.shape[0], x.shape[1]):
+            raise ValueError(f"coattn_few_query: key_padding_mask must be [B, S] = {(x.shape[0], x.shape[1])}, got {tuple(mask.shape)}")
+    return _CoattnFewQuery.apply(q, x, None if same else y, wq, bq, wk, bk, wv, bv, wo, bo, mask, splits, scaling)
 
 
 # ------------------------------------------------------------------------------------------------
