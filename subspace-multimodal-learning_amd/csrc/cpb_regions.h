@@ -977,8 +977,9 @@ struct RegionBwdLds {                    // dynamic LDS of cpb_region_bwd_kernel
   float2 dvs[16][64];                    // per-wave d vs of its key block (combined in a fixed order at the end)
 };
 
-// grid (chunks * key groups, H, B); block = 64 * nkbg * wpk threads (<= 768), nkbg = key blocks of one group (all nkb = ceil(J / 64) of
-// them up to 768 keys; more keys: groups of <= 12 key blocks, each group its own workgroups): wave w of group g owns the keys
+// grid (chunks * key groups, H, B); block = 64 * nkbg * wpk threads (<= 768; 12 waves, three per SIMD, unless the chunk has fewer than
+// wpk tiles), nkbg = key blocks of one group (a divisor of 12 chosen by region_bwd_plan; the nkb = ceil(J / 64) key blocks are dealt to
+// nkb / nkbg groups, each group its own workgroups): wave w of group g owns the keys
 // lane * nkb + g * nkbg + (w % nkbg) (lane = key; keys of one
 // wave are nkb apart, so that its lanes fall into different regions: no same-address serialisation of the LDS adds) and every wpk-th
 // query tile (32 queries) of the chunk.  For each of its tiles a lane reads its key's 32 d scores and 32 region ids (one 128-byte and
@@ -1023,12 +1024,13 @@ __global__ __launch_bounds__(768) void cpb_region_bwd_kernel(
   // (the division runs on the vector unit: back to scalar registers)
   const int kb = grp * nkbg + __builtin_amdgcn_readfirstlane(wave % nkbg), tslot = __builtin_amdgcn_readfirstlane(wave / nkbg);   // waves beyond nkbg * wpk do not exist (block size)
   const int key = lane * nkb + kb;
-  const bool kvalid = key < J && kb < nkb;                          // (the last key group may have key blocks to spare: kb >= nkb would alias lane + 1's keys)
+  const bool kvalid = key < J && kb < nkb;                          // (defensive, no plan has key blocks to spare in a group: kb >= nkb would alias lane + 1's keys)
   const int keyc = min(key, J - 1);
   const size_t vrow = (size_t)(b * (MH ? G : H) + g) * J;            // the sample positions of the head's offset group
   const float vs0 = VS[(vrow + keyc) * 2], vs1 = VS[(vrow + keyc) * 2 + 1];
   const int ntq = (N + QT - 1) / QT;
-  const int t_begin = chunk * tiles_per_chunk, t_end = min(t_begin + tiles_per_chunk, ntq);
+  // (defensive: a wave whose key block did not exist would have no tiles and go straight to the barrier and the flushes below)
+  const int t_begin = chunk * tiles_per_chunk, t_end = kb < nkb ? min(t_begin + tiles_per_chunk, ntq) : t_begin;
   float dv0 = 0.f, dv1 = 0.f;
   unsigned bad = 0u;                                                // MH: a non-finite d score seen by this lane
   // The current run of this lane: its region, the three moment sums of d bias and the two sums of d bias * d p / d offset (d vs of a run is
@@ -1357,6 +1359,23 @@ __global__ __launch_bounds__(256) void region_final2_kernel(const double* __rest
 // host side shared by the fp32-grade (deform_attn.hip) and the 16-bit (deform_attn16.hip) region entry points
 // ------------------------------------------------------------------------------------------------
 static int ceil_log2_u64(unsigned long long x) { int k = 0; while ((1ull << k) < x && k < 63) ++k; return k; }
+constexpr double REGION_BWD_FILL = 0.9;  // region_bwd_plan: workgroups / (rounds x CUs), the occupancy of all rounds of a launch together, that is enough
+constexpr int REGION_BWD_MAX_CHUNKS = 64;
+// Compute units of the current device, asked once per process; 256 (MI355X) where there is no device: the sizing entry points also run
+// on hosts without one (CPU tests, the host-sanitizer walk).  Workspace sizing and launch go through the same plan, hence the same value.
+// The region workspace byte counts (the d vs slab has one part per chunk) therefore depend on the device's CU count; the value is kept per
+// translation unit (the fp32-grade and the 16-bit entry points each ask once), the same wherever the devices of a process are alike.
+static int region_bwd_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+      (void)hipGetLastError();       // (no device: not an error of the caller's)
+      n = 256;
+    }
+    return n;
+  }();
+  return cus;
+}
 struct RegionBwdPlan {
   int chunks, tiles_per_chunk, nkb, nkbg, ngrp, wpk, kbits, shift;
   size_t amax, hist, grad, dvs, part, total;       // byte offsets behind the dq / dkv workspace
@@ -1365,15 +1384,38 @@ struct RegionBwdPlan {
 static RegionBwdPlan region_bwd_plan(int B, int N, int J, int H, int outputs = 1) {
   RegionBwdPlan p;
   const int ntq = (N + QT - 1) / QT;
-  p.chunks = (512 + B * H - 1) / (B * H);
-  if (p.chunks < 1) p.chunks = 1;
-  if (p.chunks > ntq) p.chunks = ntq;
+  // A workgroup has 12 waves wherever it can: three per SIMD, the most that 168 registers and 89 KB of LDS (one workgroup per CU) allow;
+  // any other count loads the four SIMDs unevenly (ten waves: 3, 3, 2, 2) and the crowded ones decide the workgroup's duration.  The 12 waves are
+  // nkbg key blocks x wpk waves per key block, nkbg the largest of {12, 6, 4, 3, 2, 1} that divides nkb: every wave owns a real key
+  // block (no plan pads a group, so kb >= nkb does not occur in the kernels; their tests of it are defensive).  The key blocks go to
+  // ngrp = nkb / nkbg groups, each with workgroups of its own.
+  p.nkb = (J + 63) / 64;
+  p.nkbg = 1;
+  for (const int c : {12, 6, 4, 3, 2})
+    if (p.nkb % c == 0) { p.nkbg = c; break; }
+  p.ngrp = p.nkb / p.nkbg;
+  p.wpk = 12 / p.nkbg;
+  // Query chunks.  One workgroup is resident per CU and the workgroups of a launch take about equally long, so a launch of wg workgroups
+  // takes rounds = ceil(wg / CUs) workgroup durations and keeps wg / (rounds CUs) of the CU slots of those rounds busy: its occupancy.
+  // Every workgroup also zeroes 58 KB of LDS accumulators and flushes its non-zero ones with global atomics, a fixed cost that grows
+  // with the workgroup count.  Hence the FEWEST chunks whose occupancy is at least REGION_BWD_FILL (the highest occupancy where none
+  // reaches it), and never more than leave every wave of a workgroup a tile.  This is not a test of the last round alone: the headline
+  // (B H = 64, 625 keys) gets 3 chunks = 960 workgroups = 3.75 rounds, occupancy 960 / 1024 = 0.94 with a last round 3/4 full, and
+  // measures faster than 4 chunks = 5.0 rounds.  An empirical rule: it picks the fastest candidate measured at each of four shapes
+  // (DESIGN.md section 5), all of them with the 2-D kernel; the 1-D kernel (several workgroups per CU) only shares the plan.
+  const long long base = (long long)p.ngrp * B * H, cus = region_bwd_cus();
+  const int cmax = ntq / p.wpk < 1 ? 1 : (ntq / p.wpk < REGION_BWD_MAX_CHUNKS ? ntq / p.wpk : REGION_BWD_MAX_CHUNKS);
+  double best_occ = -1.0;
+  p.chunks = 1;
+  for (int c = 1; c <= cmax; ++c) {
+    const int tpc = (ntq + c - 1) / c, eff = (ntq + tpc - 1) / tpc;      // chunks that c really gives
+    const long long wg = eff * base, rounds = (wg + cus - 1) / cus;
+    const double occ = (double)wg / (double)(rounds * cus);
+    if (occ > best_occ + 1e-9) { best_occ = occ; p.chunks = eff; }
+    if (occ >= REGION_BWD_FILL) { p.chunks = eff; break; }
+  }
   p.tiles_per_chunk = (ntq + p.chunks - 1) / p.chunks;
   p.chunks = (ntq + p.tiles_per_chunk - 1) / p.tiles_per_chunk;
-  p.nkb = (J + 63) / 64;
-  p.ngrp = (p.nkb + 11) / 12;                  // at most 12 waves per workgroup (three per SIMD at <= 168 registers): more than 768 keys
-  p.nkbg = (p.nkb + p.ngrp - 1) / p.ngrp;      // are split into groups of key blocks, each group with workgroups of its own
-  p.wpk = 12 / p.nkbg;
   if (p.wpk > p.tiles_per_chunk) p.wpk = p.tiles_per_chunk;
   // fixed point: |d bias (1, p0, p1)| <= 4 amax (|p| <= log(1 + |d|) < 4 for any reachable offset); a workgroup adds at most
   // tiles_per_chunk 32 J values into an LDS accumulator, the launch at most B H N J into a global one - both stay below 2^62

@@ -483,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void deform_attn_bwd_dq_kernel(
 // ------------------------------------------------------------------------------------------------
 // backward pass 2 (key owners): dV = P_dropped^T dO, dK = scale * dS^T Q.  A workgroup owns 128 keys (one 32-key
 // tile per wave) and one slice of the query tiles; its four waves consume the same Q / dO tile from LDS (staged
-// once per workgroup as three bf16 planes each, double-buffered, the next tile's global loads in flight during the
+// once per workgroup as two bf16 planes each (hi / mid), double-buffered, the next tile's global loads in flight during the
 // MFMAs).  Both contractions are three-term bf16 products on the 16-bit matrix pipe (48 MFMAs per tile): the A operands
 // Q^T / dO^T (lane = d, 8 queries) are gathered from the row-major planes by ds_read_b64_tr_b16, the B operands P and
 // dS are split from registers.  The partial sums of the query slices go to slabs [nparts][B, J, H*64] that
@@ -495,8 +495,8 @@ __global__ __launch_bounds__(256, 2) void deform_attn_bwd_dkv_kernel(
     const float* __restrict__ LT, const float* __restrict__ dLT, float* __restrict__ dKp,
     float* __restrict__ dVp, int N, int J, int H, int NST, int nkg, int tiles_per_part, int nparts, int Bn, DropCfg dc_in) {
   const DropCfg dc = drop_resolve(dc_in);
-  __shared__ __attribute__((aligned(16))) __bf16 Qp[2][3][QT * QBLD];         // plane 2 of both: neither written nor read since dK / dV take two terms
-  __shared__ __attribute__((aligned(16))) __bf16 dOp[2][3][QT * QBLD];
+  __shared__ __attribute__((aligned(16))) __bf16 Qp[2][2][QT * QBLD];         // [buffer][hi / mid plane]: dK / dV take two terms
+  __shared__ __attribute__((aligned(16))) __bf16 dOp[2][2][QT * QBLD];
   __shared__ __attribute__((aligned(16))) float nls[2][QT];   // -lse (times log2 e on the fast path) of the tile's queries
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, hf = lane >> 5;
   // XCD-aware block order: workgroups go to the 8 XCDs (each with its own L2) round-robin by linear id.  The nkg key groups

@@ -369,7 +369,8 @@ __global__ void cpb_final_kernel(const float* __restrict__ part_in, int nchunks,
   }
 }
 
-// query slices of backward pass 2: enough workgroups to fill the chip a few times over, at most 16 slabs
+// query slices of backward pass 2: enough workgroups to fill the chip a few times over, at most 16 slabs.  (Sizing the slices by whole
+// rounds of the 2 x CUs resident workgroups was measured and is no gain at the headline shape: DESIGN.md section 5.)
 static int dkv_parts(int B, int N, int J, int H) {
   const int nkg = (J + DKV_KEYS - 1) / DKV_KEYS, nqt = (N + QT - 1) / QT;
   const long base = (long)nkg * H * B;
