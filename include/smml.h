@@ -106,6 +106,22 @@ int smml_gemm_b16_batched(const void* A, const void* B, void* C, const float* bi
                           long long ldc, int trans, int out_bf16, int splitk, int nb, long long sa, long long sb, long long sc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Grouped 1x1 convolution on token-major data (to_q / to_k / to_v, models/DeformableAttention2D.py:218-221, DeformableAttention1D.py:150-153)
+ * as three streaming kernels, for the group shapes smml_grouped_pointwise_applies accepts (16 input and 64 output channels per group, any
+ * number of groups and rows):   y[m, cout_g g + o] = sum_i x[m, cin_g g + i] w[cout_g g + o, i]
+ * x [rows, groups cin_g], w [groups cout_g, cin_g], y / dy [rows, groups cout_g], all dense fp32; x, dy and w 16-byte aligned.
+ * fwd and dx give the bits of the same product issued as a batch over the groups through smml_gemm_f32; dw [groups cout_g, cin_g] is
+ * OVERWRITTEN with a sum in a fixed order (per-workgroup partials in the workspace, no float atomics): deterministic in every mode. */
+int smml_grouped_pointwise_applies(int groups, int cin_g, int cout_g);
+int smml_grouped_pointwise_fwd_f32(const float* x, const float* w, float* y, long long rows, int groups, int cin_g, int cout_g, void* stream);
+int smml_grouped_pointwise_dx_f32(const float* dy, const float* w, float* dx, long long rows, int groups, int cin_g, int cout_g, void* stream);
+/* workspace: W groups cout_g cin_g 4 bytes with W = ceil(rows / rpw) workgroups of rpw = max(64, ceil(rows / 256) rounded up to a multiple
+ * of 32) rows, 16-byte aligned. */
+size_t smml_grouped_pointwise_dw_workspace_bytes(long long rows, int groups, int cin_g, int cout_g);
+int smml_grouped_pointwise_dw_f32(const float* dy, const float* x, float* dw, long long rows, int groups, int cin_g, int cout_g,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim C (<= 1024) of x [R, C]; saves mean / rstd per row.
  * Replaces nn.LayerNorm at models/DeformCrossTransMIL.py:44,71,75,90,144 and mil.py:175,187. */
 int smml_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean,
