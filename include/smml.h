@@ -14,7 +14,10 @@
  *     (thread-local: the one piece of per-thread state the library keeps); no exception crosses the boundary;
  *   - "accumulated into" outputs must be zeroed (or hold a running sum) by the caller;
  *   - fixed widths of the two fused attention families (no other value is built, the entry points return an error):
- *     head dim 64; position-bias MLP posdim -> 32 -> 32 -> heads / groups (the reference's dim = 128), heads / groups <= 2.
+ *     head dim 64; position-bias MLP posdim -> 32 -> 32 -> heads / groups (the reference's dim = 128), heads / groups <= 2;
+ *   - parameter NAMES are binding, not only types and order: the Python side calls the deformable-attention entry points by them
+ *     (_capi.bind), so one meaning keeps one name across entry points (q, tables, logits_t / logits16, H, G, posdim, dtype, ...);
+ *     tests/test_named_launch.py fails if a prototype names a parameter the caller's namespace does not hold.
  */
 #ifndef SMML_H_
 #define SMML_H_

@@ -43,16 +43,17 @@ def _ctype(ctext: str, where: str, ret: bool = False):
 
 
 def _declarator(text: str, where: str):
-    """`type name` -> (ctypes type, name)"""
+    """`type name` -> (name, ctypes type, the type is `float*` / `const float*`)"""
     m = re.fullmatch(r"\s*([\w\s]*[\w*])\s*\b([A-Za-z_]\w*)\s*", text)
     if not m or m.group(2) in ("int", "long", "float", "void", "unsigned", "size_t", "char", "short", "const"):
         raise RuntimeError(f"include/smml.h: cannot read `{text.strip()}` of `{where}` as `type name`")
-    return _ctype(m.group(1), where), m.group(2)
+    return m.group(2), _ctype(m.group(1), where), re.sub(r"\bconst\b|\s", "", m.group(1)) == "float*"
 
 
-def parse_prototypes(text: str) -> dict:
+def parse_prototypes(text: str, params: Optional[dict] = None) -> dict:
     """name -> (restype, [argtypes]) for C text that holds prototypes `ret smml_name(type name, ...);` and nothing else besides
-    comments, preprocessor lines and the extern "C" bracket.  Strict: whatever it cannot read raises, with the offending text."""
+    comments, preprocessor lines and the extern "C" bracket.  Strict: whatever it cannot read raises, with the offending text.
+    params (a dict) receives name -> [(parameter name, ctypes type, pointee is float)]: what `bind` calls an entry point by."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
     text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
@@ -64,28 +65,33 @@ def parse_prototypes(text: str) -> dict:
         m = re.fullmatch(r"\s*([\w\s*]+?)\b(smml_\w+)\s*\(([^()]*)\)\s*", proto)
         if not m or m.group(2) in sigs:
             raise RuntimeError(f"include/smml.h: cannot read `{' '.join(proto.split())}` as one prototype `ret smml_name(type name, ...)`")
-        ret, name, params = m.groups()
-        args = [] if params.strip() == "void" else [_declarator(p, name)[0] for p in params.split(",")]
-        sigs[name] = (_ctype(ret, name, ret=True), args)
+        ret, name, plist = m.groups()
+        decl = [] if plist.strip() == "void" else [_declarator(p, name) for p in plist.split(",")]
+        sigs[name] = (_ctype(ret, name, ret=True), [t for _, t, _ in decl])
+        if params is not None:
+            params[name] = decl
     return sigs
 
 
-def parse_header(text: str):
-    """(SMML_ABI_VERSION, the fields of SmmlDeformOpts, name -> (restype, [argtypes])) of the text of include/smml.h"""
+def parse_header(text: str, params: Optional[dict] = None):
+    """(SMML_ABI_VERSION, the fields of SmmlDeformOpts, name -> (restype, [argtypes])) of the text of include/smml.h; params: as in
+    parse_prototypes"""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     abi = re.search(r"^[ \t]*#[ \t]*define[ \t]+SMML_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
     struct = re.search(r"typedef\s+struct\s+SmmlDeformOpts\s*\{(.*?)\}\s*SmmlDeformOpts\s*;", text, re.S)
     if not abi or not struct:
         raise RuntimeError("include/smml.h: SMML_ABI_VERSION or struct SmmlDeformOpts not found")
-    fields = [_declarator(f, "SmmlDeformOpts")[::-1] for f in struct.group(1).split(";") if f.strip()]
-    return int(abi.group(1)), fields, parse_prototypes(text[:struct.start()] + text[struct.end():])
+    fields = [_declarator(f, "SmmlDeformOpts")[:2] for f in struct.group(1).split(";") if f.strip()]
+    return int(abi.group(1)), fields, parse_prototypes(text[:struct.start()] + text[struct.end():], params)
 
 
 if not os.path.exists(HEADER_PATH):
     raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it (it ships with the repository, next to the package)")
-# ABI_VERSION: smml_abi_version() of the library this binding is for; SIGNATURES: name -> (restype, argtypes), as the header declares them
+# ABI_VERSION: smml_abi_version() of the library this binding is for; SIGNATURES: name -> (restype, argtypes), as the header declares them;
+# PARAMS: name -> [(parameter name, ctypes type, pointee is float)] - the header's parameter names are binding: `bind` calls by them
+PARAMS: dict = {}
 with open(HEADER_PATH) as _h:
-    ABI_VERSION, DeformOpts._fields_, SIGNATURES = parse_header(_h.read())
+    ABI_VERSION, DeformOpts._fields_, SIGNATURES = parse_header(_h.read(), PARAMS)
 
 _lib: Optional[C.CDLL] = None
 
@@ -157,3 +163,35 @@ def fptr(t: Optional[torch.Tensor]):
 def stream(device=None):
     """The current HIP stream of `device` (default: the current device) as a void*."""
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _plan(decl):
+    """[(parameter name, what turns a tensor into that argument)] of one prototype's PARAMS row: fptr for a `float*` (the fp32 check),
+    ptr for any other pointer"""
+    return [(pname, fptr if is_float else ptr if ctype is C.c_void_p else None) for pname, ctype, is_float in decl]
+
+
+_PLANS = {name: _plan(decl) for name, decl in PARAMS.items()}     # resolved once: a launch costs one lookup per parameter
+
+
+def bind(name: str, values, params: Optional[dict] = None) -> list:
+    """The arguments of the entry point `name` in its prototype's order, each taken from the mapping `values` by its parameter name
+    (`values` may hold more: one namespace serves every entry point of a family).  Tensors become device pointers - fptr for a
+    `float*` parameter, ptr for any other pointer; None is NULL; scalars and ready-made c_void_p / byref values pass unchanged.
+    params: prototypes other than the header's (parse_prototypes; tests)."""
+    out = []
+    for pname, conv in _PLANS[name] if params is None else _plan(params[name]):
+        try:
+            v = values[pname]
+        except KeyError:
+            raise RuntimeError(f"{name}: no value for its parameter `{pname}`") from None
+        out.append(conv(v) if conv is not None and isinstance(v, torch.Tensor) else v)
+    return out
+
+
+def call(name: str, values, keys=None):
+    """What the entry point `name` returns for the arguments `bind` takes from `values` (a status for check(), or a size).  keys: the
+    key set the caller states for this namespace (a constant a test can hold against the header); `values` must hold exactly those."""
+    if keys is not None and values.keys() != keys:
+        raise RuntimeError(f"{name}: the namespace holds {sorted(values)}, its key set names {sorted(keys)}")
+    return getattr(lib(), name)(*bind(name, values))

@@ -135,12 +135,10 @@ def relu_masks_rows(masks):
 def relu1_masks(vs, gq, w1, b1, *, B: int, N: int, J: int, groups: int, log_distance: bool = True):
     """Layer-1 ReLU decisions of the position-bias MLP as the kernels evaluate them: int16 [(B G), J, 2, nst] in the bit order of the
     saved layer-2 masks (include/smml.h smml_deform_attn_relu1_masks).  Tests only."""
-    L = capi.lib()
-    nst = L.smml_deform_attn_nst(N)
-    out = torch.empty(B * groups, J, 2, nst, device=vs.device, dtype=torch.int16)
-    capi.check(L.smml_deform_attn_relu1_masks(capi.fptr(_c(vs)), capi.fptr(_c(gq)), capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.ptr(out),
-                                              B, N, J, groups, vs.shape[-1], capi.stream(), capi.deform_opts(log_distance=bool(log_distance))),
-               "relu1_masks")
+    out = torch.empty(B * groups, J, 2, capi.lib().smml_deform_attn_nst(N), device=vs.device, dtype=torch.int16)
+    ns = dict(vs=_c(vs), gq=_c(gq), w1=_c(w1), b1=_c(b1), masks=out, B=B, N=N, J=J, G=groups, posdim=vs.shape[-1], stream=capi.stream(),
+              opts=capi.deform_opts(log_distance=bool(log_distance)))
+    capi.check(capi.call("smml_deform_attn_relu1_masks", ns, RELU1_KEYS), "relu1_masks")
     return out
 
 
@@ -1506,13 +1504,13 @@ def _dtype16(compute_dtype):
 
 
 # layer-2 decisions of a cpb_table='forward' backward: 'table' (mask table, include/smml.h) or 'recompute' (layer 2 per pair); measurement / test switch
-TABLE_FORWARD_MASKS = __import__("os").environ.get("SMML_TABFWD_MASKS", "table")
+TABLE_FORWARD_MASKS = os.environ.get("SMML_TABFWD_MASKS", "table")
 
 
 # fp32-grade path, 2-D positions: the position bias per LINEAR REGION of its MLP (csrc/cpb_regions.h, include/smml.h) - exact, and the
 # default wherever it applies (signed-log offsets, one head per offset group, J <= REGION_MAX_KEYS).  SMML_CPB_REGIONS=0 keeps the per-pair MLP
 # kernels (the cross-check of tests/test_gpu_regions.py, and the path of every other configuration).
-CPB_REGIONS = __import__("os").environ.get("SMML_CPB_REGIONS", "1") != "0"
+CPB_REGIONS = os.environ.get("SMML_CPB_REGIONS", "1") != "0"
 REGION_MAX_KEYS = 16384      # RG_MAX_KEYS of csrc/cpb_regions.h
 REGION_LDS_CAP = 0           # tests: regions with an id >= this take the global-memory path of the region kernels (0: the default, 2048)
 
@@ -1571,15 +1569,17 @@ def cpb_regions_build(w1, b1, w2, b2, w3, b3, pmax: float, tables: Optional[torc
     """The region tables of the position-bias MLP with these parameters over [-pmax, pmax]^2 (uint8 scratch owned by the caller), built
     on the current stream.  w3 [outputs, 32] with outputs = heads per offset group: a second output adds its (a, c) (one buffer size
     for both)."""
-    L = capi.lib()
-    nbytes = L.smml_cpb_regions_bytes()
-    if tables is None:
-        tables = torch.empty(nbytes, device=w1.device, dtype=torch.uint8)
-    w = (capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.fptr(_c(w2)), capi.fptr(_c(b2)), capi.fptr(_c(w3)), capi.fptr(_c(b3)))
-    if w3.shape[0] == 1:
-        capi.check(L.smml_cpb_regions_build(*w, float(pmax), capi.ptr(tables), nbytes, capi.stream()), "cpb_regions_build")
-    else:
-        capi.check(L.smml_cpb_regions_mh_build(*w, int(w3.shape[0]), float(pmax), capi.ptr(tables), nbytes, capi.stream()), "cpb_regions_mh_build")
+    return _tables_build("cpb_regions_build" if w3.shape[0] == 1 else "cpb_regions_mh_build", capi.lib().smml_cpb_regions_bytes(),
+                         (w1, b1, w2, b2, w3, b3), pmax, tables)
+
+
+def _tables_build(entry: str, nbytes: int, mlp, pmax: float, tables: Optional[torch.Tensor]) -> torch.Tensor:
+    """The 2-D region tables or the 1-D piece tables of the bias MLP `mlp` = (w1, b1, w2, b2, w3, b3), into `tables` (None: allocated)."""
+    tables = torch.empty(nbytes, device=mlp[0].device, dtype=torch.uint8) if tables is None else tables
+    w1, b1, w2, b2, w3, b3 = (_c(t) for t in mlp)
+    ns = dict(w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, outputs=int(w3.shape[0]), pmax=float(pmax), tables=tables, tables_bytes=nbytes,
+              stream=capi.stream())
+    capi.check(capi.call("smml_" + entry, ns, BUILD_KEYS), entry)
     return tables
 
 
@@ -1608,14 +1608,7 @@ def region1d_tables_view(tables: torch.Tensor):
 def cpb_regions1d_build(w1, b1, w2, b2, w3, b3, pmax: float = 0.0, tables: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The piece tables of the 1-D position-bias MLP with these parameters (index grid over [-pmax, pmax]; 0: the span of the breakpoints),
     built on the current stream into uint8 scratch owned by the caller."""
-    L = capi.lib()
-    nbytes = L.smml_cpb_regions1d_bytes()
-    if tables is None:
-        tables = torch.empty(nbytes, device=w1.device, dtype=torch.uint8)
-    capi.check(L.smml_cpb_regions1d_build(capi.fptr(_c(w1)), capi.fptr(_c(b1)), capi.fptr(_c(w2)), capi.fptr(_c(b2)), capi.fptr(_c(w3)),
-                                          capi.fptr(_c(b3)), int(w3.shape[0]), float(pmax), capi.ptr(tables), nbytes, capi.stream()),
-               "cpb_regions1d_build")
-    return tables
+    return _tables_build("cpb_regions1d_build", capi.lib().smml_cpb_regions1d_bytes(), (w1, b1, w2, b2, w3, b3), pmax, tables)
 
 
 def _region_why(posdim: int, keys: int, w2_shape, w3_shape, heads: int, groups: int, compute_dtype, cpb_table, cpb_regions, log_distance: bool,
@@ -1784,13 +1777,14 @@ def _core_done(ctx, inputs, out, lse, logits, side=(), scores=None, tap=None):
     return out
 
 
-def _core_backward(ctx, dout, logits, like, wsb: int, ws_dtype=torch.float32):
+def _core_backward(ctx, dout, logits, like, ws_keys: frozenset, dims: dict, ws_dtype=torch.float32):
     """The buffers of a fused core's backward: dout (contiguous), the d scores (the scores' shape; fp32, 16-bit core: bf16), one
-    gradient per tensor of `like`, the workspace of wsb bytes."""
+    gradient per tensor of `like`, the workspace and its size in bytes - what the core's size function answers for `dims`."""
     dout = _c(dout)
+    wsb = capi.call(core_entry_points(ctx.path, ctx.multi_head, ctx.cfg[5] is not None)[2], dims, ws_keys)
     dlogits = torch.empty(logits.shape, device=logits.device, dtype=torch.float32 if ctx.cfg[5] is None else torch.bfloat16)
     grads = tuple(torch.empty_like(t) for t in like)
-    return dout, dlogits, grads, torch.empty(wsb if ws_dtype == torch.uint8 else (wsb + 3) // 4, device=dout.device, dtype=ws_dtype)
+    return dout, dlogits, grads, torch.empty(wsb if ws_dtype == torch.uint8 else (wsb + 3) // 4, device=dout.device, dtype=ws_dtype), wsb
 
 
 def _grads(ctx, *grads):
@@ -1803,39 +1797,55 @@ def _grads(ctx, *grads):
 
 
 # (the core deform_path names, multi-head, 16-bit) -> the stems of its forward's and its backward's entry point in include/smml.h ("smml_" +
-# stem + "_fwd" / "_bwd", "_f32" behind the fp32-grade ones; stem + "_fwd" / "_bwd" is the capi.check name too), the workspace-size function
-# of the backward, the TIMER events of the forward and of the bias backward
-_WS = "smml_deform_attn_{}bwd_workspace_bytes"
+# stem + "_fwd" / "_bwd", "_f32" behind the fp32-grade ones; stem + "_fwd" / "_bwd" is the capi.check name too), the TIMER events of the
+# forward and of the bias backward.  No argument lists: a launch takes its arguments by name (capi.bind) from a namespace - see below.
 _CORE_ENTRY = {
-    ("pair", False, False): ("deform_attn", "deform_attn", _WS.format(""), "deform_attn_fwd", "cpb_bwd"),
-    ("pair", False, True): ("deform_attn16", "deform_attn16", _WS.format(""), "deform16_fwd", "cpb16_bwd"),
-    ("pair_table_forward", False, True): ("deform_attn_table", "deform_attn16", _WS.format(""), "deform_table_fwd", "cpb16_bwd"),
-    ("pair_wide", False, False): ("deform_attn_wide", "deform_attn_wide", _WS.format("wide_"), "deform_wide_fwd", "cpb_wide_bwd"),
-    ("table", False, True): ("deform_attn_table", "deform_attn_table", _WS.format("table_"), "deform_table_fwd", "cpb_table_bwd"),
-    ("region1d", False, False): ("deform_attn_region1d", "deform_attn_region1d", _WS.format("region1d_"), "deform_region1d_fwd", "cpb_region1d_bwd"),
-    ("region", False, False): ("deform_attn_region", "deform_attn_region", _WS.format("region_"), "deform_region_fwd", "cpb_region_bwd"),
-    ("region", False, True): ("deform_attn16_region", "deform_attn16_region", _WS.format("region_"), "deform16_region_fwd", "cpb16_region_bwd"),
-    ("region", True, False): ("deform_attn_region_mh", "deform_attn_region_mh", _WS.format("region_mh_"), "deform_region_mh_fwd", "cpb_region_mh_bwd"),
-    ("region", True, True): ("deform_attn16_region_mh", "deform_attn16_region_mh", _WS.format("region_mh_"), "deform16_region_mh_fwd",
-                             "cpb16_region_mh_bwd"),
+    ("pair", False, False): ("deform_attn", "deform_attn", "deform_attn_fwd", "cpb_bwd"),
+    ("pair", False, True): ("deform_attn16", "deform_attn16", "deform16_fwd", "cpb16_bwd"),
+    ("pair_table_forward", False, True): ("deform_attn_table", "deform_attn16", "deform_table_fwd", "cpb16_bwd"),
+    ("pair_wide", False, False): ("deform_attn_wide", "deform_attn_wide", "deform_wide_fwd", "cpb_wide_bwd"),
+    ("table", False, True): ("deform_attn_table", "deform_attn_table", "deform_table_fwd", "cpb_table_bwd"),
+    ("region1d", False, False): ("deform_attn_region1d", "deform_attn_region1d", "deform_region1d_fwd", "cpb_region1d_bwd"),
+    ("region", False, False): ("deform_attn_region", "deform_attn_region", "deform_region_fwd", "cpb_region_bwd"),
+    ("region", False, True): ("deform_attn16_region", "deform_attn16_region", "deform16_region_fwd", "cpb16_region_bwd"),
+    ("region", True, False): ("deform_attn_region_mh", "deform_attn_region_mh", "deform_region_mh_fwd", "cpb_region_mh_bwd"),
+    ("region", True, True): ("deform_attn16_region_mh", "deform_attn16_region_mh", "deform16_region_mh_fwd", "cpb16_region_mh_bwd"),
 }
 
 
-def _core_entry(ctx):
-    return _CORE_ENTRY[(ctx.path, ctx.multi_head, ctx.cfg[5] is not None)]
+# A namespace holds all the call has under include/smml.h's parameter names: a score-shaped tensor under each name a prototype gives it,
+# None where the core has no use for a value.  The key sets (tests/test_named_launch.py holds them against the header):
+_RUN = "scale dropout_p dropout_seed dtype ev_start ev_stop stream opts"
+_MLP = "q k v vs gq w1 b1 w2 b2 w3 b3 tables out lse logits_t logits16 relu_masks region_ids B N J H G W posdim " + _RUN
+_TABLE = "q k v vs gq table out lse logits16 B N J H G posdim table_g table_pmax " + _RUN
+_BWD = " dout dq dk dv dvs workspace workspace_bytes "
+MLP_WS_KEYS, TABLE_WS_KEYS = frozenset("B N J H G W".split()), frozenset("B N J H posdim".split())
+MLP_FWD_KEYS = frozenset((_MLP + " table table_g table_pmax bias_t").split())
+MLP_BWD_KEYS = frozenset((_MLP + _BWD + "dlogits_t dlogits16 dw1 db1 dw2 db2 dw3 db3").split())
+TABLE_FWD_KEYS = frozenset(_TABLE.split())
+TABLE_BWD_KEYS = frozenset((_TABLE + _BWD + "dlogits16 dtable grid_h grid_w").split())
+BUILD_KEYS = frozenset("w1 b1 w2 b2 w3 b3 outputs pmax tables tables_bytes stream".split())
+MASK_TABLE_KEYS = frozenset("w1 b1 w2 b2 table posdim pmax stream".split())
+RELU1_KEYS = frozenset("vs gq w1 b1 masks B N J G posdim stream opts".split())
+WIDE_DECISIONS_KEYS = RELU1_KEYS | {"w2", "b2", "W"}
+DROPOUT_MASK_KEYS = frozenset("mask B N J H dropout_p dropout_seed stream opts".split())
 
 
-def _launch(ctx, direction: str, q, k, opts, *args):
-    """This call's launch in `direction` ('fwd' / 'bwd'): every entry point ends with (TIMER events, stream, opts)."""
-    e = _core_entry(ctx)
-    stem, ev = (e[0], e[3]) if direction == "fwd" else (e[1], e[4])
-    fn = getattr(capi.lib(), f"smml_{stem}_{direction}" + ("_f32" if ctx.cfg[5] is None else ""))
-    pairs = q.shape[0] * ctx.cfg[0] * q.shape[1] * k.shape[1]
-    capi.check(fn(*args, *TIMER.events(ev, pairs), capi.stream(), opts), f"{stem}_{direction}")
+def core_entry_points(path: str, multi_head: bool, m16: bool):
+    """A core's forward, backward and backward-workspace-size function in include/smml.h (a 16-bit core shares its sibling's size)."""
+    (fwd, bwd), f32 = _CORE_ENTRY[(path, multi_head, m16)][:2], "" if m16 else "_f32"
+    return f"smml_{fwd}_fwd{f32}", f"smml_{bwd}_bwd{f32}", f"smml_{bwd.replace('attn16', 'attn')}_bwd_workspace_bytes"
+
+
+def _launch(ctx, direction: str, keys: frozenset, ns: dict):
+    """This call's launch in `direction` ('fwd' / 'bwd') from the namespace `ns`, plus the TIMER events and the stream."""
+    core, bwd = (ctx.path, ctx.multi_head, ctx.cfg[5] is not None), direction == "bwd"
+    ns["ev_start"], ns["ev_stop"], ns["stream"] = *TIMER.events(_CORE_ENTRY[core][2 + bwd], ns["B"] * ns["H"] * ns["N"] * ns["J"]), capi.stream()
+    capi.check(capi.call(core_entry_points(*core)[bwd], ns, keys), f"{_CORE_ENTRY[core][bwd]}_{direction}")
 
 
 _REGION_STREAMS = {}
-REGION_PREFETCH = __import__("os").environ.get("SMML_REGION_PREFETCH", "1") != "0"
+REGION_PREFETCH = os.environ.get("SMML_REGION_PREFETCH", "1") != "0"
 
 
 class RegionPrefetch:
@@ -1878,9 +1888,10 @@ def wide_decisions(vs, gq, w1, b1, w2, b2, *, B: int, N: int, J: int, groups: in
     (smml_deform_attn_wide_decisions) -> (m1, m2) bool [(B groups), N, J, W]: [x1 > 0], [x2 > 0] per pair and hidden channel."""
     W = w2.shape[0]
     words = torch.empty(B * groups, N, J, 2, W // 32, device=vs.device, dtype=torch.int32)
-    capi.check(capi.lib().smml_deform_attn_wide_decisions(*(capi.fptr(_c(t.detach())) for t in (vs, gq, w1, b1, w2, b2)), capi.ptr(words), B, N, J,
-                                                          groups, W, vs.shape[-1], capi.stream(), capi.deform_opts(None, log_distance)),
-               "deform_attn_wide_decisions")
+    vs, gq, w1, b1, w2, b2 = (_c(t.detach()) for t in (vs, gq, w1, b1, w2, b2))
+    ns = dict(vs=vs, gq=gq, w1=w1, b1=b1, w2=w2, b2=b2, masks=words, B=B, N=N, J=J, G=groups, W=W, posdim=vs.shape[-1], stream=capi.stream(),
+              opts=capi.deform_opts(None, log_distance))
+    capi.check(capi.call("smml_deform_attn_wide_decisions", ns, WIDE_DECISIONS_KEYS), "deform_attn_wide_decisions")
     bits = ((words[..., None] >> torch.arange(32, device=vs.device, dtype=torch.int32)) & 1).bool()      # [..., 2, W / 32, 32]
     bits = bits.reshape(B * groups, N, J, 2, W)
     return bits[..., 0, :], bits[..., 1, :]
@@ -1946,8 +1957,7 @@ class _DeformAttnMLP(torch.autograd.Function):
                      or tuple(b2.shape) != (W,)):
             raise RuntimeError(f"the wide position-bias MLP is {posdim} -> {W} -> {W} -> heads // groups; got w1 {tuple(w1.shape)}, "
                                f"w3 {tuple(w3.shape)}")
-        L = capi.lib()
-        tables = None
+        tables = table = bias = points = tpmax = None
         if path == "region1d":
             tables = cpb_regions1d_build(w1, b1, w2, b2, w3, b3, float(pmax or 0.0))
         elif region and prefetch is not None and prefetch.matches(w1, b1, w2, b2, w3, b3, pmax):
@@ -1957,31 +1967,25 @@ class _DeformAttnMLP(torch.autograd.Function):
         out, lse, logits = _core_outputs(ctx, q, heads, J, m16, scores)
         ctx.table_pmax = pmax if path == "pair_table_forward" else None
         ctx.export_masks = side = None               # side: the score-shaped tensor the core saves beside the scores
-        qkv, mlp = tuple(capi.fptr(t) for t in inputs[:5]), tuple(capi.fptr(t) for t in inputs[5:])
-        run = (float(scale), float(dropout_p), int(dropout_seed)) + (() if m16 is None else (m16[0],))
-        if region:
-            if logits is not None:
-                side = _score_tiles(q, heads, J, torch.int16)                 # the linear piece of every pair, per head
-            hg = (heads, groups) if path == "region1d" or ctx.multi_head else (heads,)
-            args = (*qkv, *(mlp if path == "region" else ()), capi.ptr(tables), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(side),
-                    B, N, J, *hg, *run)                                       # (the 1-D tables carry the parameters)
-        elif path == "pair":
-            if logits is not None:
-                side = _score_tiles(q, heads, J, torch.int16, 2)              # layer-2 ReLU decisions of the bias MLP (per lane half)
-            args = (*qkv, *mlp, capi.fptr(out), capi.fptr(lse), capi.ptr(logits), capi.ptr(side), B, N, J, heads, groups, posdim, *run)
-        elif wide:
+        if region and logits is not None:
+            side = _score_tiles(q, heads, J, torch.int16)                     # the linear piece of every pair, per head
+        elif path == "pair" and logits is not None:
+            side = _score_tiles(q, heads, J, torch.int16, 2)                  # layer-2 ReLU decisions of the bias MLP (per lane half)
+        elif wide and logits is None:
             # training: the bias tiles are built in logits_t and overwritten in place by the scores; inference: a scratch buffer of that size
             # (a call that hands out its scores takes the training form: the same launch, the scores kept)
-            bias = _score_tiles(q, heads, J, torch.float32) if logits is None else None
-            args = (*qkv, *mlp, capi.fptr(out), capi.fptr(lse), capi.fptr(logits), capi.fptr(bias), B, N, J, heads, groups, W, posdim, *run)
-        else:
+            bias = _score_tiles(q, heads, J, torch.float32)
+        elif path == "pair_table_forward":
             if logits is not None and DECISION_TAP is not None:               # tests: the backward writes the decisions it recomputed here
                 ctx.export_masks = _score_tiles(q, heads, J, torch.int16, 2).zero_()
             with torch.no_grad():
                 table = cpb_table_fn(w1, b1, w2, b2, w3, b3, posdim=posdim, pmax=pmax, device=q.device)
-            args = (*qkv, capi.fptr(table), capi.fptr(out), capi.fptr(lse), capi.ptr(logits), B, N, J, heads, groups, posdim,
-                    L.smml_deform_attn_table_points(posdim), float(pmax), *run)
-        _launch(ctx, "fwd", q, k, capi.deform_opts(seed_offset, ctx.log_distance, region_lds_cap=REGION_LDS_CAP if region else 0), *args)
+            points, tpmax = capi.lib().smml_deform_attn_table_points(posdim), float(pmax)
+        _launch(ctx, "fwd", MLP_FWD_KEYS, dict(
+            q=q, k=k, v=v, vs=vs, gq=gq, w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, tables=tables, table=table, out=out, lse=lse,
+            logits_t=logits, logits16=logits, relu_masks=side, region_ids=side, bias_t=bias, B=B, N=N, J=J, H=heads, G=groups, W=W,
+            posdim=posdim, table_g=points, table_pmax=tpmax, scale=float(scale), dropout_p=float(dropout_p), dropout_seed=int(dropout_seed),
+            dtype=m16 and m16[0], opts=capi.deform_opts(seed_offset, ctx.log_distance, region_lds_cap=REGION_LDS_CAP if region else 0)))
         tap = None
         if DECISION_TAP is not None and region:
             # the 1-D ids index the piece tables (region1d_tables_view), not the 2-D region tables: keys of their own
@@ -1998,40 +2002,29 @@ class _DeformAttnMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        *inputs, out, lse, logits, side, tables = ctx.saved_tensors
-        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3 = inputs
+        q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, out, lse, logits, side, tables = ctx.saved_tensors
         heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
         (B, N, _), J, posdim, W = q.shape, k.shape[1], vs.shape[-1], w2.shape[0]
         path, region = ctx.path, ctx.path in ("region", "region1d")
-        L = capi.lib()
-        ws_dims = (heads, groups, W) if path == "pair_wide" else (heads, groups) if ctx.multi_head else (heads,)
-        wsb = getattr(L, _core_entry(ctx)[2])(B, N, J, *ws_dims)
-        dout, dlogits, grads, ws = _core_backward(ctx, dout, logits, (q, k, v, vs, w1, b1, w2, b2, w3, b3), wsb,
-                                                  torch.uint8 if region else torch.float32)
-        gp = tuple(capi.fptr(g) for g in grads)
-        run = (scale, dropout_p, dropout_seed) + (() if m16 is None else (m16[0],))
+        dout, dlogits, (dq, dk, dv, dvs, dw1, db1, dw2, db2, dw3, db3), ws, wsb = _core_backward(
+            ctx, dout, logits, (q, k, v, vs, w1, b1, w2, b2, w3, b3), MLP_WS_KEYS, dict(B=B, N=N, J=J, H=heads, G=groups, W=W),
+            torch.uint8 if region else torch.float32)
         opts = capi.deform_opts(ctx.seed_offset, ctx.log_distance, region_lds_cap=REGION_LDS_CAP if region else 0)
-        if region:
-            hg = (heads, groups) if path == "region1d" or ctx.multi_head else (heads,)
-            args = (*(capi.fptr(t) for t in inputs[:5 if path == "region1d" else 11]), capi.ptr(tables), capi.fptr(out), capi.fptr(dout),
-                    capi.fptr(lse), capi.ptr(logits), capi.ptr(side), capi.ptr(dlogits), *gp, capi.ptr(ws), wsb, B, N, J, *hg, *run)
-        elif path == "pair_wide":
-            args = (*(capi.fptr(t) for t in (*inputs, out, dout, lse, logits, dlogits)), *gp, capi.fptr(ws), wsb, B, N, J, heads, groups, W,
-                    posdim, *run)
-        else:
+        if path in ("pair", "pair_table_forward") and m16 is not None:
             mtab = None
             if path == "pair_table_forward" and TABLE_FORWARD_MASKS == "table":
                 # layer-2 decisions from a mask table (include/smml.h) built from the current weights - one small launch
-                cells = L.smml_cpb_mask_table_cells(posdim)
+                cells = capi.lib().smml_cpb_mask_table_cells(posdim)
                 mtab = torch.empty(cells ** posdim, device=q.device, dtype=torch.int32)
-                capi.check(L.smml_cpb_mask_table(capi.fptr(w1), capi.fptr(b1), capi.fptr(w2), capi.fptr(b2), capi.ptr(mtab), posdim,
-                                                 float(ctx.table_pmax), capi.stream()), "cpb_mask_table")
-            if m16 is not None:
-                opts = capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)
-            args = (*(capi.fptr(t) for t in (*inputs, out, dout, lse)), capi.ptr(logits), capi.ptr(side), capi.ptr(dlogits), *gp, capi.fptr(ws),
-                    wsb, B, N, J, heads, groups, posdim, *run)
-        _launch(ctx, "bwd", q, k, opts, *args)
-        return _grads(ctx, *grads[:4], None, *grads[4:])
+                ns = dict(w1=w1, b1=b1, w2=w2, b2=b2, table=mtab, posdim=posdim, pmax=float(ctx.table_pmax), stream=capi.stream())
+                capi.check(capi.call("smml_cpb_mask_table", ns, MASK_TABLE_KEYS), "cpb_mask_table")
+            opts = capi.deform_opts(ctx.seed_offset, ctx.log_distance, mtab, float(ctx.table_pmax or 0.0), ctx.export_masks)
+        _launch(ctx, "bwd", MLP_BWD_KEYS, dict(
+            q=q, k=k, v=v, vs=vs, gq=gq, w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, tables=tables, out=out, dout=dout, lse=lse,
+            logits_t=logits, logits16=logits, relu_masks=side, region_ids=side, dlogits_t=dlogits, dlogits16=dlogits, dq=dq, dk=dk, dv=dv,
+            dvs=dvs, dw1=dw1, db1=db1, dw2=dw2, db2=db2, dw3=dw3, db3=db3, workspace=ws, workspace_bytes=wsb, B=B, N=N, J=J, H=heads,
+            G=groups, W=W, posdim=posdim, scale=scale, dropout_p=dropout_p, dropout_seed=dropout_seed, dtype=m16 and m16[0], opts=opts))
+        return _grads(ctx, dq, dk, dv, dvs, None, dw1, db1, dw2, db2, dw3, db3)
 
 
 class _DeformAttnTable(torch.autograd.Function):
@@ -2047,30 +2040,33 @@ class _DeformAttnTable(torch.autograd.Function):
         points = capi.lib().smml_deform_attn_table_points(posdim)
         if tuple(table.shape) != (heads // groups, points ** posdim):
             raise RuntimeError(f"table must be [{heads // groups}, {points ** posdim}] (got {tuple(table.shape)})")
-        ctx.table = (points, float(pmax)) + (tuple(int(x) for x in grid) if grid else (0, 0))
+        grid_h, grid_w = (int(x) for x in grid) if grid else (0, 0)
+        ctx.table = dict(table_g=points, table_pmax=float(pmax), grid_h=grid_h, grid_w=grid_w)
         out, lse, logits = _core_outputs(ctx, q, heads, J, m16)
-        _launch(ctx, "fwd", q, k, capi.deform_opts(seed_offset), *(capi.fptr(t) for t in (*inputs, out, lse)), capi.ptr(logits), B, N, J, heads,
-                groups, posdim, points, float(pmax), float(scale), float(dropout_p), int(dropout_seed), m16[0])
+        _launch(ctx, "fwd", TABLE_FWD_KEYS, dict(
+            q=q, k=k, v=v, vs=vs, gq=gq, table=table, out=out, lse=lse, logits16=logits, B=B, N=N, J=J, H=heads, G=groups, posdim=posdim,
+            table_g=points, table_pmax=float(pmax), scale=float(scale), dropout_p=float(dropout_p), dropout_seed=int(dropout_seed),
+            dtype=m16[0], opts=capi.deform_opts(seed_offset)))
         # no per-pair ReLU decisions in this mode: the MLP runs on grid points only
         return _core_done(ctx, inputs, out, lse, logits, tap={"masks2": None, "table_pmax": float(pmax)})
 
     @staticmethod
     def backward(ctx, dout):
-        *inputs, out, lse, logits = ctx.saved_tensors
-        q, k, v, vs, gq, table = inputs
+        q, k, v, vs, gq, table, out, lse, logits = ctx.saved_tensors
         heads, groups, scale, dropout_p, dropout_seed, m16 = ctx.cfg
         (B, N, _), J, posdim = q.shape, k.shape[1], vs.shape[-1]
-        wsb = getattr(capi.lib(), _core_entry(ctx)[2])(B, N, J, heads, posdim)
-        dout, dlogits, grads, ws = _core_backward(ctx, dout, logits, (q, k, v, vs, table), wsb)
-        _launch(ctx, "bwd", q, k, capi.deform_opts(ctx.seed_offset), *(capi.fptr(t) for t in (*inputs, out, dout, lse)), capi.ptr(logits),
-                capi.ptr(dlogits), *(capi.fptr(g) for g in grads), capi.fptr(ws), wsb, B, N, J, heads, groups, posdim, *ctx.table, scale,
-                dropout_p, dropout_seed, m16[0])
-        return _grads(ctx, *grads[:4], None, grads[4])
+        dout, dlogits, (dq, dk, dv, dvs, dtable), ws, wsb = _core_backward(ctx, dout, logits, (q, k, v, vs, table), TABLE_WS_KEYS,
+                                                                           dict(B=B, N=N, J=J, H=heads, posdim=posdim))
+        _launch(ctx, "bwd", TABLE_BWD_KEYS, dict(
+            ctx.table, q=q, k=k, v=v, vs=vs, gq=gq, table=table, out=out, dout=dout, lse=lse, logits16=logits, dlogits16=dlogits, dq=dq,
+            dk=dk, dv=dv, dvs=dvs, dtable=dtable, workspace=ws, workspace_bytes=wsb, B=B, N=N, J=J, H=heads, G=groups, posdim=posdim,
+            scale=scale, dropout_p=dropout_p, dropout_seed=dropout_seed, dtype=m16[0], opts=capi.deform_opts(ctx.seed_offset)))
+        return _grads(ctx, dq, dk, dv, dvs, None, dtable)
 
 
 def table_pmax(gq_bound: float, vs_bound: float) -> float:
     """Half-width of the table in signed-log units for |gq| <= gq_bound, |vs| <= vs_bound (positions beyond it take the edge value)."""
-    return float(__import__("math").log1p(gq_bound + vs_bound) * 1.0001)
+    return float(math.log1p(gq_bound + vs_bound) * 1.0001)
 
 
 _REPLAY_COUNTER = {}         # device index -> int64 [1]: bumped once per dropout call inside a captured graph
@@ -2153,9 +2149,9 @@ def deform_attention(q, k, v, vs, gq, w1, b1, w2, b2, w3, b3, *, heads: int, gro
 def deform_attention_dropout_mask(B: int, N: int, J: int, H: int, dropout_p: float, dropout_seed: int, device, seed_offset=None):
     """The keep mask (0 / 1) [B, H, N, J] a launch with this (p, seed[, device-resident replay offset]) applies; tests only."""
     mask = torch.empty(B, H, N, J, device=device, dtype=torch.float32)
-    L = capi.lib()
-    capi.check(L.smml_deform_attn_dropout_mask_f32(capi.fptr(mask), B, N, J, H, float(dropout_p), int(dropout_seed),
-                                                   capi.stream(), capi.deform_opts(seed_offset)), "dropout_mask")
+    ns = dict(mask=mask, B=B, N=N, J=J, H=H, dropout_p=float(dropout_p), dropout_seed=int(dropout_seed), stream=capi.stream(),
+              opts=capi.deform_opts(seed_offset))
+    capi.check(capi.call("smml_deform_attn_dropout_mask_f32", ns, DROPOUT_MASK_KEYS), "dropout_mask")
     return mask
 
 
