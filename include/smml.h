@@ -689,6 +689,48 @@ int smml_fewq_attn_bwd_f32(const float* u, const float* x, const float* y, const
                            long long y_batch_stride, long long y_row_stride, long long dx_batch_stride, long long dx_row_stride,
                            long long dy_batch_stride, long long dy_row_stride, int splits, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sets of at most 8 tokens (MCAT_Surv after its co-attention, models/model.py:589-651: nn.TransformerEncoder with 8 heads over the 4 genomic
+ * tokens, then Attn_Net_Gated + softmax + bmm).  A token set is a few KB and its cost is launches: every entry point below is ONE launch, with no
+ * workspace and no float atomics - the results are a function of the inputs alone.
+ *
+ * Self-attention from a packed projection.  qkv holds the rows [q | k | v] of width 3 E of (sample b, token t) at
+ * qkv + b qkv_batch_stride + t qkv_token_stride (floats, multiples of 4, tokens at least 3 E apart: the sequence-first [T, B, 3 E] output of one
+ * smml_gemm_f32 is read in place, a batch-first one as well); head h of H reads columns [h hd, (h + 1) hd) of each third, hd = E / H.
+ *   S = scale Q K^T   P = softmax_rows(S) (the row maximum is subtracted)   O = (P keep) V
+ *   o: rows of width E with the heads merged, at o + b o_batch_stride + t o_token_stride   p [B, H, T, T] dense: the softmax BEFORE keep
+ *   keep [B, H, T, T] dense or null: float multipliers of attention dropout, 0 or 1 / (1 - rate), drawn by the caller.  A row whose keep is all
+ *   zero gives a zero output row and zero score gradients.
+ *   1 <= T <= 8, E a multiple of 64 up to 512, hd 32 or 64, any B >= 1 (anything else is an error, nothing is launched); qkv, o, dout, dqkv
+ *   16-byte aligned.
+ * Backward, for dout (rows of width E, strides of their own), the saved p and the same keep:
+ *   dV = (P keep)^T dO   dP = (dO V^T) keep   dS = P (dP - rowsum(dP P))   dQ = scale dS K   dK = scale dS^T Q
+ * written as rows [dq | dk | dv] into dqkv (strides of its own, every element overwritten). */
+int smml_token_attn_fwd_f32(const float* qkv, const float* keep, float* o, float* p, int B, int T, int E, int H, long long qkv_batch_stride,
+                            long long qkv_token_stride, long long o_batch_stride, long long o_token_stride, float scale, void* stream);
+int smml_token_attn_bwd_f32(const float* qkv, const float* keep, const float* p, const float* dout, float* dqkv, int B, int T, int E, int H,
+                            long long qkv_batch_stride, long long qkv_token_stride, long long dout_batch_stride, long long dout_token_stride,
+                            long long dqkv_batch_stride, long long dqkv_token_stride, float scale, void* stream);
+
+/* Gated attention pooling over a token set, WITH the gradient of the pooled rows (smml_attn_pool_gated_* pools a bag of features and forms none).
+ *   s[b, t] = sum_d w[d] hv[b, t, d] hu[b, t, d] + b      a[b, :] = softmax_t(s[b, :])      out[b, :] = sum_t a[b, t] x[b, t, :]
+ *   x: rows of width E at x + b x_batch_stride + t x_token_stride (as qkv above, tokens at least E apart)   h2 [B, T, 2 D] dense, the layout of
+ *   smml_attn_pool_gated_*: columns [0, D) hold hv (tanh), columns [D, 2 D) hold hu (sigmoid)   w [D]   b [1] (device memory)
+ *   s [B, T]   a [B, T]   out [B, E]
+ *   1 <= T <= 8, E a multiple of 64 up to 512, D a multiple of 64 up to 256, any B >= 1 (anything else is an error, nothing is launched);
+ *   x, h2, w, out, dout, dx, dh2 16-byte aligned.
+ * Backward, for dout [B, E] and the saved a: tau[b, t] = dout[b] . x[b, t], ds = a (tau - sum_t a tau) (the dots and their mean are kept in
+ * fp64 up to the difference: the tokens of a set can lie close together, and tau - sum_t a tau then cancels to a few digits);
+ *   dx[b, t, :] = a[b, t] dout[b, :] (strides of its own)   dh2 [B, T, 2 D] = ds w hu | ds w hv (the gradient of h2)
+ *   dw [D] = sum_{b, t} ds hv hu   db [1] = sum_{b, t} ds      all overwritten.
+ * dw and db are formed by ONE workgroup of the launch, which re-forms ds of every sample and adds in a fixed order (four interleaved ascending
+ * runs over the samples, then the four runs in order); the other workgroups own one sample's dx and dh2 each. */
+int smml_token_pool_gated_fwd_f32(const float* x, const float* h2, const float* w, const float* b, float* s, float* a, float* out, int B, int T,
+                                  int E, int D, long long x_batch_stride, long long x_token_stride, void* stream);
+int smml_token_pool_gated_bwd_f32(const float* x, const float* h2, const float* w, const float* a, const float* dout, float* dx, float* dh2,
+                                  float* dw, float* db, int B, int T, int E, int D, long long x_batch_stride, long long x_token_stride,
+                                  long long dx_batch_stride, long long dx_token_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .coattention import MultiheadAttention  # noqa: F401
 from .cmta import CMTA, SNN_Block, Transformer_G, Transformer_P  # noqa: F401
 from .fusion import BilinearFusion, define_bifusion  # noqa: F401
 from .mil import ABMIL, GatedABMIL  # noqa: F401
+from .mcat import MCAT_Surv, Attn_Net_Gated, TransformerEncoder, TransformerEncoderLayer  # noqa: F401
 from .pathomic import DeformPathomicNet, MaxNet, define_net  # noqa: F401
 from .losses import BatchLoss, GatherLayer, OrthogonalLoss  # noqa: F401
 from .data_parallel import BagDataParallel  # noqa: F401
@@ -25,7 +26,7 @@ from .train_step import PinnedBagStager, allreduce_scores_then_modulate, gradien
 
 __all__ = [
     "CPB", "Scale", "DeformCrossAttention1D", "DeformCrossAttention2D", "FusionNet", "DeformCrossTransLayer",
-    "DeformCrossTransMIL", "Pooler", "NystromAttention", "TransLayer", "PPEG", "TransMIL", "moore_penrose_iter_pinv", "MultiheadAttention", "CMTA", "Transformer_P", "Transformer_G", "SNN_Block", "BilinearFusion", "define_bifusion", "MaxNet", "ABMIL", "GatedABMIL", "DeformPathomicNet", "define_net", "BatchLoss", "GatherLayer",
+    "DeformCrossTransMIL", "Pooler", "NystromAttention", "TransLayer", "PPEG", "TransMIL", "moore_penrose_iter_pinv", "MultiheadAttention", "CMTA", "Transformer_P", "Transformer_G", "SNN_Block", "BilinearFusion", "define_bifusion", "MaxNet", "ABMIL", "GatedABMIL", "MCAT_Surv", "Attn_Net_Gated", "TransformerEncoder", "TransformerEncoderLayer", "DeformPathomicNet", "define_net", "BatchLoss", "GatherLayer",
     "OrthogonalLoss", "BagDataParallel", "gradient_modulate", "gradient_modulate_survival", "PinnedBagStager", "BagStore", "BagStoreWriter", "BagStoreDataset", "fixdim_gather", "fixdim_indices", "functional", "synth", "lib",
     "deterministic", "set_deterministic", "is_deterministic",
 ]

@@ -46,7 +46,8 @@ class deterministic:
     Covered: the fp32-grade and 16-bit deform paths (DeformPathomicNet, both attn_dim values), BatchLoss, the co-attention
     MultiheadAttention and ABMIL (the attention-pooling kernels have a single form that is deterministic by construction - per-split
     partials merged in a fixed order - and the switch only selects the fixed-order reductions of the hidden layer's gradients; the
-    few-query co-attention kernels are of the same kind, the switch selects the fixed-order forms of the weight gradients around them).  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
+    few-query co-attention kernels are of the same kind, the switch selects the fixed-order forms of the weight gradients around them; the token-set kernels of MCAT_Surv have one form, fixed-order by
+    construction).  An operation whose kernel still adds floats with atomics - the table modes of the position bias, the
     bf16-storage GEMM with a split reduction, the depthwise-convolution weight gradients of the Nystrom block and of PPEG - raises
     RuntimeError under the switch; there is no silent fall-back.
 
@@ -866,6 +867,179 @@ def coattn_few_query(q, x, y, wq, bq, wk, bk, wv, bv, wo, bo, *, scaling: float,
         if tuple(mask.shape) != (x.shape[0], x.shape[1]):
             raise ValueError(f"coattn_few_query: key_padding_mask must be [B, S] = {(x.shape[0], x.shape[1])}, got {tuple(mask.shape)}")
     return _CoattnFewQuery.apply(q, x, None if same else y, wq, bq, wk, bk, wv, bv, wo, bo, mask, splits, scaling)
+
+
+# ------------------------------------------------------------------------------------------------
+# sets of at most 8 tokens (MCAT_Surv after its co-attention, models/model.py:589-651; csrc/token_set.hip): multi-head self-attention from
+# the packed projection and gated attention pooling WITH the gradient of the pooled rows - one launch per direction each, no workspace,
+# no float atomics.  The launches take their arguments by the header's parameter names (capi.call); the key sets:
+# ------------------------------------------------------------------------------------------------
+TOKEN_MAX_T, TOKEN_MAX_E, TOKEN_MAX_D = 8, 512, 256
+TOKEN_HEAD_DIMS = (32, 64)
+_TOKEN_ATTN = "qkv keep B T E H qkv_batch_stride qkv_token_stride scale stream "
+_TOKEN_POOL = "x h2 w B T E D x_batch_stride x_token_stride stream "
+TOKEN_ATTN_FWD_KEYS = frozenset((_TOKEN_ATTN + "o p o_batch_stride o_token_stride").split())
+TOKEN_ATTN_BWD_KEYS = frozenset((_TOKEN_ATTN + "p dout dqkv dout_batch_stride dout_token_stride dqkv_batch_stride dqkv_token_stride").split())
+TOKEN_POOL_FWD_KEYS = frozenset((_TOKEN_POOL + "b s a out").split())
+TOKEN_POOL_BWD_KEYS = frozenset((_TOKEN_POOL + "a dout dx dh2 dw db dx_batch_stride dx_token_stride").split())
+
+
+def token_why(*, T: int, E: int, heads: Optional[int] = None, D: Optional[int] = None, attn_mask: bool = False,
+              key_padding_mask: bool = False, fused: bool = True) -> Optional[str]:
+    """Why an operation on a set of T tokens of width E stays on its composed form; None: it takes the token-set kernels.  heads: the
+    call is a self-attention with that many heads (composed: coattention.MultiheadAttention - projections, permutes, matmul4,
+    softmax_rows, matmul4).  D: the call is a gated pooling with D hidden units per gate (composed: softmax_rows and matmul4 after the
+    head's three layers).  No GPU work."""
+    if not fused:
+        return "the fused token-set path is switched off"
+    if not 1 <= T <= TOKEN_MAX_T:
+        return f"{T} tokens (at most {TOKEN_MAX_T})"
+    if E % 64 or not 0 < E <= TOKEN_MAX_E:
+        return f"token width {E} (a multiple of 64 up to {TOKEN_MAX_E})"
+    if heads is not None:
+        if heads < 1 or E % heads or E // heads not in TOKEN_HEAD_DIMS:
+            return f"head dim {E}/{heads} (the kernels are built for {' and '.join(map(str, TOKEN_HEAD_DIMS))})"
+        if attn_mask:
+            return "an attention mask (the token kernels take none)"
+        if key_padding_mask:
+            return "a key padding mask (the token kernels take none)"
+    if D is not None and (D % 64 or not 0 < D <= TOKEN_MAX_D):
+        return f"{D} hidden units per gate (a multiple of 64 up to {TOKEN_MAX_D})"
+    return None
+
+
+def token_path(**kw) -> str:
+    """'token' (csrc/token_set.hip) or 'composed': the arguments of token_why, which names the reason for 'composed'."""
+    return "composed" if token_why(**kw) is not None else "token"
+
+
+def _like_rows(t: torch.Tensor, width: int) -> torch.Tensor:
+    """An uninitialised [B, T, width] buffer in the layout of the rows t [B, T, .]: sequence-first memory where t's is (what follows reads
+    it sequence-first without a copy), batch-first otherwise."""
+    B, T = t.shape[:2]
+    if t.transpose(0, 1).is_contiguous():
+        return torch.empty(T, B, width, device=t.device, dtype=torch.float32).transpose(0, 1)
+    return torch.empty(B, T, width, device=t.device, dtype=torch.float32)
+
+
+def _token_attn_check(qkv, heads: int, keep):
+    """Shapes the token self-attention kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if qkv.dim() != 3 or qkv.shape[-1] % 3:
+        raise ValueError(f"token_self_attention: need the packed projection qkv [B, T, 3 E], got {tuple(qkv.shape)}")
+    B, T, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    if B < 1:
+        raise ValueError(f"token_self_attention: empty batch ({tuple(qkv.shape)})")
+    why = token_why(T=T, E=E, heads=int(heads))
+    if why is not None:
+        raise ValueError(f"token_self_attention: {why}")
+    if keep is not None and tuple(keep.shape) != (B, heads, T, T):
+        raise ValueError(f"token_self_attention: keep must be [B, H, T, T] = {(B, heads, T, T)}, got {tuple(keep.shape)}")
+    return B, T, E
+
+
+class _TokenSelfAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, keep, heads, scale):
+        B, T, E = _token_attn_check(qkv, heads, keep)
+        qkv = _rows(qkv)
+        keep = _c(keep) if keep is not None else None
+        o = _like_rows(qkv, E)
+        p = torch.empty(B, heads, T, T, device=qkv.device, dtype=torch.float32)
+        ctx.dims = dict(B=B, T=T, E=E, H=int(heads), scale=float(scale))
+        ns = dict(ctx.dims, qkv=_rows_ptr(qkv), keep=keep, o=_rows_ptr(o), p=p, qkv_batch_stride=_bs(qkv), qkv_token_stride=qkv.stride(1),
+                  o_batch_stride=_bs(o), o_token_stride=o.stride(1), stream=capi.stream())
+        capi.check(capi.call("smml_token_attn_fwd_f32", ns, TOKEN_ATTN_FWD_KEYS), "token_attn_fwd")
+        ctx.save_for_backward(qkv, keep, p)
+        ctx.mark_non_differentiable(p)
+        return o, p
+
+    @staticmethod
+    def backward(ctx, dout, _dp):
+        qkv, keep, p = ctx.saved_tensors
+        dout = _rows(dout)
+        dqkv = _grad_rows(qkv)
+        ns = dict(ctx.dims, qkv=_rows_ptr(qkv), keep=keep, p=p, dout=_rows_ptr(dout), dqkv=_rows_ptr(dqkv), qkv_batch_stride=_bs(qkv),
+                  qkv_token_stride=qkv.stride(1), dout_batch_stride=_bs(dout), dout_token_stride=dout.stride(1),
+                  dqkv_batch_stride=_bs(dqkv), dqkv_token_stride=dqkv.stride(1), stream=capi.stream())
+        capi.check(capi.call("smml_token_attn_bwd_f32", ns, TOKEN_ATTN_BWD_KEYS), "token_attn_bwd")
+        return dqkv, None, None, None
+
+
+def token_self_attention(qkv, *, heads: int, scale: Optional[float] = None, keep=None, probs_out=None):
+    """o [B, T, E] = (softmax_rows(scale Q K^T) keep) V per head, heads merged, for a set of T <= 8 tokens from its packed projection
+    qkv [B, T, 3 E] = [q | k | v] (head h reads columns [h hd, (h + 1) hd) of each third, hd = E / heads in {32, 64}; E a multiple of 64 up to
+    512; other shapes raise ValueError before anything is launched).  qkv is read in place when its columns are contiguous: pass the
+    sequence-first output [T, B, 3 E] of `linear` as its transpose(0, 1); o then comes back in the same memory order, and so does the
+    gradient of qkv.  scale: default hd ** -0.5.  keep [B, H, T, T]: the multipliers of attention dropout, 0 or 1 / (1 - rate), drawn by
+    the caller (no gradient); a row of zeros gives a zero output row.  probs_out: a list that receives [p], the softmax [B, H, T, T] before
+    keep.  One launch per direction, identical bits run after run."""
+    _token_attn_check(qkv, heads, keep)
+    if scale is None:
+        scale = float(qkv.shape[-1] // 3 // heads) ** -0.5
+    o, p = _TokenSelfAttention.apply(qkv, keep, int(heads), float(scale))
+    if probs_out is not None:
+        probs_out[:] = [p]
+    return o
+
+
+def _token_pool_check(x, h2, w, b):
+    """Shapes the token pooling kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if x.dim() != 3 or h2.dim() != 3 or tuple(h2.shape[:2]) != tuple(x.shape[:2]) or h2.shape[-1] % 2:
+        raise ValueError(f"token_pool_gated: need x [B, T, E] and h2 [B, T, 2 D] over the same tokens, got {tuple(x.shape)} and {tuple(h2.shape)}")
+    B, T, E = x.shape
+    D = h2.shape[-1] // 2
+    if B < 1:
+        raise ValueError(f"token_pool_gated: empty batch ({tuple(x.shape)})")
+    why = token_why(T=T, E=E, D=D)
+    if why is not None:
+        raise ValueError(f"token_pool_gated: {why}")
+    if w.numel() != D or b.numel() != 1:
+        raise ValueError(f"token_pool_gated: one attention map - w must hold D = {D} values and b one, got {tuple(w.shape)} and {tuple(b.shape)}")
+    return B, T, E, D
+
+
+class _TokenPoolGated(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h2, w, b, scores_out):
+        B, T, E, D = _token_pool_check(x, h2, w, b)
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        x = _rows(x); h2 = _c(h2); w = _c(w).reshape(D); b = _c(b).reshape(1)
+        s = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        a = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        M = torch.empty(B, E, device=x.device, dtype=torch.float32)
+        ctx.dims = dict(B=B, T=T, E=E, D=D)
+        ns = dict(ctx.dims, x=_rows_ptr(x), h2=h2, w=w, b=b, s=s, a=a, out=M, x_batch_stride=_bs(x), x_token_stride=x.stride(1),
+                  stream=capi.stream())
+        capi.check(capi.call("smml_token_pool_gated_fwd_f32", ns, TOKEN_POOL_FWD_KEYS), "token_pool_gated_fwd")
+        if scores_out is not None:
+            scores_out[:] = [s, a]
+        ctx.save_for_backward(x, h2, w, a)
+        return M
+
+    @staticmethod
+    def backward(ctx, dM):
+        x, h2, w, a = ctx.saved_tensors
+        dM = _c(dM)
+        dx = _grad_rows(x)
+        dh2 = torch.empty_like(h2)
+        dw = torch.empty(ctx.dims["D"], device=x.device, dtype=torch.float32)
+        db = torch.empty(1, device=x.device, dtype=torch.float32)
+        ns = dict(ctx.dims, x=_rows_ptr(x), h2=h2, w=w, a=a, dout=dM, dx=_rows_ptr(dx), dh2=dh2, dw=dw, db=db, x_batch_stride=_bs(x),
+                  x_token_stride=x.stride(1), dx_batch_stride=_bs(dx), dx_token_stride=dx.stride(1), stream=capi.stream())
+        capi.check(capi.call("smml_token_pool_gated_bwd_f32", ns, TOKEN_POOL_BWD_KEYS), "token_pool_gated_bwd")
+        return dx, dh2, dw.view(ctx.w_shape), db.view(ctx.b_shape), None
+
+
+def token_pool_gated(x, h2, w, b, *, scores_out=None):
+    """M [B, E] = sum_t softmax_t(sum_d w_d hv[b, t, d] hu[b, t, d] + b) x[b, t, :] for a set of T <= 8 tokens x [B, T, E] and its two gates in
+    ONE tensor h2 [B, T, 2 D] (hv = h2[..., :D], the tanh units; hu = h2[..., D:], the sigmoid units: the output of
+    linear(..., act=ACT_TANH_SIGMOID) with the stacked weight); one attention map: w holds D values, b one.  E a multiple of 64 up to 512,
+    D a multiple of 64 up to 256; other shapes raise ValueError before anything is launched.  x is read in place when its columns are
+    contiguous (the transpose of a sequence-first tensor).  Unlike attention_pool_gated the pooled rows are activations: x, h2, w and b
+    all receive gradients.  scores_out: a list that receives [s, a], the scores and their softmax, both [B, T].  One launch per direction;
+    the sums over samples in dw and db have one owner and a fixed order: identical bits run after run."""
+    _token_pool_check(x, h2, w, b)
+    return _TokenPoolGated.apply(x, h2, w, b, scores_out)
 
 
 # ------------------------------------------------------------------------------------------------
