@@ -129,6 +129,18 @@ int smml_grouped_pointwise_dw_f32(const float* dy, const float* x, float* dw, lo
  * Replaces nn.LayerNorm at models/DeformCrossTransMIL.py:44,71,75,90,144 and mil.py:175,187. */
 int smml_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean,
                            float* rstd, long long R, int C, float eps, void* stream);
+/* The mean over a bag's tokens of LayerNorm(x) (the path's final norm, DeformCrossTransMIL.py:144 and Pooler's mean :193) in one pass over
+ * x [nb, n, C] that never stores the normalised tensor: out[b, c] += (1 / n) sum_r LayerNorm(x)[b, r, c], out [nb, C] accumulated into
+ * (the caller zeroes it); mean / rstd [nb n] are smml_layernorm_fwd_f32's, bit for bit.  C = 128 only, x / gamma / beta 16-byte aligned:
+ * any other call is an error (compose smml_layernorm_fwd_f32 and smml_colsum_f32 instead). */
+int smml_layernorm_fwd_mean_f32(const float* x, const float* gamma, const float* beta, float* mean, float* rstd, float* out, int nb,
+                                long long n, int C, float eps, void* stream);
+/* Deterministic form: out OVERWRITTEN.  A bag's rows are cut into chunks of rpc = 64 rows (n <= 1024: 512; beyond n = 131 072:
+ * ceil(n / 2048) rounded up to a multiple of 32) - a function of n alone, the same in both forms; the chunk sums (scaled) go to
+ * workspace[chunk][b][C] and a second kernel adds them in a fixed order.  workspace: ceil(n / rpc) nb C 4 bytes, 16-byte aligned (0 for C != 128). */
+size_t smml_layernorm_fwd_mean_det_workspace_bytes(int nb, long long n, int C);
+int smml_layernorm_fwd_mean_det_f32(const float* x, const float* gamma, const float* beta, float* mean, float* rstd, float* out, int nb,
+                                    long long n, int C, float eps, void* workspace, size_t workspace_bytes, void* stream);
 /* dy row for x row i is dy[(i / rows_per_dy) * C + c] * dy_scale (rows_per_dy > 1 broadcasts one
  * gradient row over a token block, e.g. the gradient of Pooler's mean, DeformCrossTransMIL.py:193);
  * dx is overwritten (accumulate_dx = 0) or added to; dgamma / dbeta are accumulated into. */

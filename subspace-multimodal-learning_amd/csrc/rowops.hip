@@ -2,6 +2,7 @@
 //   LayerNorm forward / backward          (models/DeformCrossTransMIL.py:44,71,75,90,144; mil.py:175,187)
 //   column sums / means over tokens       (Pooler mean, DeformCrossTransMIL.py:193; bias gradients)
 //   ReLU backward                         (_fc1, DeformCrossTransMIL.py:83)
+//   LayerNorm + mean over tokens          (the path's final norm: one pass over x, the normalised tensor is never stored)
 // LayerNorm: the generic kernels put one wave on one row (lane l owns columns l, l + 64, ...; C <= 1024); at C = 128 - the path's token
 // width - that is one 512-byte row in flight per wave and latency-bound, so both directions have a 128-column kernel: a half-wave per
 // row, one float4 per lane, several rows of loads in flight per wave, grid-stride loop.  Partial column sums leave a workgroup
@@ -110,6 +111,69 @@ __global__ __launch_bounds__(256) void layernorm_fwd128_kernel(const float* __re
   }
 }
 
+// The mean over a bag's tokens of LayerNorm(x) without y in memory (the final norm of the path: y was written, then read back once by the
+// column sums): x [nb, n, 128]; workgroup (chunk, b) takes rows [chunk rows_per_chunk, ...) of bag b, forms each row's mean, rstd and y in
+// registers exactly as layernorm_fwd128_kernel does (mean / rstd: its bits), adds y per lane over the rows a half-wave meets, the eight
+// half-waves in ascending order, times scale (1 / n) - then out[b, c] += that (float atomics) or part[chunk][b][c] = that (deterministic form)
+__global__ __launch_bounds__(256) void layernorm_fwd128_mean_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, float* __restrict__ mean,
+                                                                    float* __restrict__ rstd, float* __restrict__ out, long long n,
+                                                                    float eps, float scale, int rows_per_chunk, float* __restrict__ part) {
+  constexpr int C = 128, U = LN128_RPT;
+  __shared__ float red[8][C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
+  const int b = blockIdx.y;
+  const bool low = hl < 16;
+  const float4 gm = *reinterpret_cast<const float4*>(gamma + 4 * hl), bt = *reinterpret_cast<const float4*>(beta + 4 * hl);
+  const long long lo_row = (long long)blockIdx.x * rows_per_chunk, hi_row = min(n, lo_row + rows_per_chunk);   // lo_row < n: the host's grid
+  const float* xb = x + (long long)b * n * C;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long long base = lo_row + wave * (2 * U); base < hi_row; base += 8 * U) {
+    float4 xv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long row = base + 2 * u + half;
+      xv[u] = *reinterpret_cast<const float4*>(xb + (row < hi_row ? row : hi_row - 1) * C + 4 * hl);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long row = base + 2 * u + half;
+      const float4 own = xv[u];
+      const float4 oth = make_float4(__shfl_xor(own.x, 16), __shfl_xor(own.y, 16), __shfl_xor(own.z, 16), __shfl_xor(own.w, 16));
+      const float4 lo = low ? own : oth, hi = low ? oth : own;
+      const float mu = row128_sum((0.f + lo.x) + hi.x, (0.f + lo.y) + hi.y, (0.f + lo.z) + hi.z, (0.f + lo.w) + hi.w) / (float)C;
+      const float4 dl = make_float4(lo.x - mu, lo.y - mu, lo.z - mu, lo.w - mu);
+      const float4 dh = make_float4(hi.x - mu, hi.y - mu, hi.z - mu, hi.w - mu);
+      const float ss = row128_sum(fmaf(dh.x, dh.x, dl.x * dl.x), fmaf(dh.y, dh.y, dl.y * dl.y), fmaf(dh.z, dh.z, dl.z * dl.z),
+                                  fmaf(dh.w, dh.w, dl.w * dl.w));
+      const float rs = rsqrtf(ss / (float)C + eps);
+      if (row < hi_row) {
+        const float4 d = low ? dl : dh;
+        acc.x += fmaf(d.x * rs, gm.x, bt.x); acc.y += fmaf(d.y * rs, gm.y, bt.y);
+        acc.z += fmaf(d.z * rs, gm.z, bt.z); acc.w += fmaf(d.w * rs, gm.w, bt.w);
+        if (hl == 0) { mean[(long long)b * n + row] = mu; rstd[(long long)b * n + row] = rs; }
+      }
+    }
+  }
+  *reinterpret_cast<float4*>(&red[wave * 2 + half][4 * hl]) = acc;
+  __syncthreads();
+  if (threadIdx.x < C) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t += red[i][threadIdx.x];
+    t *= scale;
+    if (part) part[((size_t)blockIdx.x * gridDim.y + b) * C + threadIdx.x] = t;
+    else atomicAdd(&out[(long long)b * C + threadIdx.x], t);
+  }
+}
+
+// a + b rounded once, never contracted with a product that feeds it (the compiler fuses a * b + c across statements by default, and
+// HIP's __fadd_rn is a plain +): what accumulate_dx adds must be the bits of a separate elementwise add
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 // dx (+)= rstd * (g dy - mean(g dy) - xhat * mean(g dy xhat)); dgamma += sum dy xhat; dbeta += sum dy
 // dy row for x row i is dy[(i / rows_per_dy) * C ...] * dy_scale  (rows_per_dy > 1: broadcast rows, e.g. the
 // gradient of a mean over tokens).
@@ -158,7 +222,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         const int c = lane + 64 * i;
         if (c < C) {
           const float v = rs * (gd[i] - s1 - xh[i] * s2);
-          dxr[c] = accumulate_dx ? dxr[c] + v : v;
+          dxr[c] = accumulate_dx ? add_rn(dxr[c], v) : v;       // a separate add's bits (no contraction with the product)
         }
       }
     }
@@ -188,26 +252,31 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
-// C = 128 (the path's token width): a half-wave per row, one float4 per lane, two row pairs per trip - four rows of
-// loads in flight per wave instead of one (the generic kernel is latency-bound at 128 columns)
+// C = 128 (the path's token width): a half-wave per row, one float4 per lane, LN128_BWD_RPT = two row pairs per trip - four rows of
+// loads (x and dy) in flight per wave instead of one (the generic kernel is latency-bound at 128 columns).  Four row pairs per trip, as
+// in the forward sibling (122 registers, no scratch), were measured inside the training step at 80 000 rows and are no faster: 42.6 /
+// 41.7 -> 42.5 us per plain call - the kernel is not short of loads in flight.  The arithmetic of a row does not
+// depend on the trip it falls into: dx is the same bits for any U and grid.
+// accumulate_dx: the old dx of all the trip's rows is loaded before the first store, and added with a non-contracted +.
+constexpr int LN128_BWD_RPT = 2;
 __global__ __launch_bounds__(256) void layernorm_bwd128_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                const float* __restrict__ gamma, const float* __restrict__ mean,
                                                                const float* __restrict__ rstd, float* __restrict__ dx,
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                long long R, long long rows_per_dy, float dy_scale,
                                                                int accumulate_dx, float* __restrict__ part) {
-  constexpr int C = 128;
+  constexpr int C = 128, U = LN128_BWD_RPT;
   __shared__ float red[2][8][C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
   const float4 gm = *reinterpret_cast<const float4*>(gamma + 4 * hl);
   float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
-  const long long stride = (long long)gridDim.x * 16;          // rows per trip of the whole grid: 4 waves x 2 halves x 2
-  for (long long r0 = ((long long)blockIdx.x * 4 + wave) * 4 + half; r0 < R; r0 += stride) {
-    float4 xv[2], dv[2];
-    float mu[2], rs[2];
-    bool ok[2];
+  const long long stride = (long long)gridDim.x * (8 * U);     // rows per trip of the whole grid: 4 waves x 2 halves x U
+  for (long long r0 = ((long long)blockIdx.x * 4 + wave) * (2 * U) + half; r0 < R; r0 += stride) {
+    float4 xv[U], dv[U];
+    float mu[U], rs[U];
+    bool ok[U];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < U; ++u) {
       const long long row = r0 + 2 * u;
       ok[u] = row < R;
       const long long rr = ok[u] ? row : R - 1;
@@ -215,8 +284,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd128_kernel(const float* __re
       dv[u] = *reinterpret_cast<const float4*>(dy + (rr / rows_per_dy) * C + 4 * hl);
       mu[u] = mean[rr]; rs[u] = rstd[rr];
     }
+    float4 ov[U];
+    if (accumulate_dx) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+      for (int u = 0; u < U; ++u) {
+        ov[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok[u]) ov[u] = *reinterpret_cast<const float4*>(dx + (r0 + 2 * u) * C + 4 * hl);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
       const float sc = ok[u] ? dy_scale : 0.f;
       const float4 d = make_float4(dv[u].x * sc, dv[u].y * sc, dv[u].z * sc, dv[u].w * sc);
       const float4 xh = make_float4((xv[u].x - mu[u]) * rs[u], (xv[u].y - mu[u]) * rs[u], (xv[u].z - mu[u]) * rs[u],
@@ -232,7 +309,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd128_kernel(const float* __re
         float4* dxr = reinterpret_cast<float4*>(dx + (r0 + 2 * u) * C + 4 * hl);
         float4 v = make_float4(rs[u] * (gd.x - s1 - xh.x * s2), rs[u] * (gd.y - s1 - xh.y * s2),
                                rs[u] * (gd.z - s1 - xh.z * s2), rs[u] * (gd.w - s1 - xh.w * s2));
-        if (accumulate_dx) { const float4 o = *dxr; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+        if (accumulate_dx) {        // one rounding of old + new (no contraction with the product above): the bits of a separate add
+          const float4 o = ov[u];
+          v = make_float4(add_rn(v.x, o.x), add_rn(v.y, o.y), add_rn(v.z, o.z), add_rn(v.w, o.w));
+        }
         *dxr = v;
       }
     }
@@ -476,6 +556,69 @@ int smml_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta
   return SMML_OK;
 }
 
+// rows per chunk of layernorm_fwd128_mean_kernel - a function of the bag length alone, the same in both forms: two trips of a workgroup
+// (64 rows), more only for bags beyond 131 072 tokens (at most 2048 chunks per bag); a multiple of the 32 rows of a trip.  Bags of up to
+// 1024 tokens keep the 512-row chunks of the column sums this kernel replaces: at most two chunks, and two atomic adds onto zero commute,
+// so small bags stay run-to-run identical in the default form as they were.
+static long long layernorm_mean_rows_per_chunk(long long n) {
+  if (n <= 1024) return 512;
+  const long long want = (n + 2047) / 2048;
+  return want <= 64 ? 64 : (want + 31) / 32 * 32;
+}
+
+static int layernorm_mean_launch(const char* fn, const float* x, const float* gamma, const float* beta, float* mean, float* rstd,
+                                 float* out, int nb, long long n, int C, float eps, float* part, void* stream) {
+  SMML_REQUIRE(x && gamma && beta && mean && rstd && out, "%s: null pointer", fn);
+  SMML_REQUIRE(nb > 0 && nb <= 65535 && n > 0, "%s: need 0 < nb <= 65535 bags of n > 0 rows", fn);
+  SMML_REQUIRE(C == 128, "%s: the fused token mean has a 128-column kernel only (got C = %d)", fn, C);
+  SMML_REQUIRE(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(gamma) | reinterpret_cast<size_t>(beta)) & 15) == 0,
+               "%s: x, gamma and beta must be 16-byte aligned", fn);
+  const long long rpc = layernorm_mean_rows_per_chunk(n), chunks = (n + rpc - 1) / rpc;
+  SMML_REQUIRE(rpc <= 2147483647LL && chunks <= 2147483647LL, "%s: too many rows", fn);
+  hipLaunchKernelGGL(layernorm_fwd128_mean_kernel, dim3((unsigned)chunks, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
+                     mean, rstd, out, n, eps, 1.f / (float)n, (int)rpc, part);
+  return SMML_OK;
+}
+
+// out [nb, C] must be zeroed by the caller; out[b, c] += (1 / n) sum_r LayerNorm(x)[b, r, c]; mean / rstd [nb n] as smml_layernorm_fwd_f32 saves them
+int smml_layernorm_fwd_mean_f32(const float* x, const float* gamma, const float* beta, float* mean, float* rstd, float* out, int nb,
+                                long long n, int C, float eps, void* stream) {
+  if (int rc = layernorm_mean_launch("smml_layernorm_fwd_mean_f32", x, gamma, beta, mean, rstd, out, nb, n, C, eps, nullptr, stream)) return rc;
+  SMML_LAUNCH_CHECK("smml_layernorm_fwd_mean_f32");
+  return SMML_OK;
+}
+
+size_t smml_layernorm_fwd_mean_det_workspace_bytes(int nb, long long n, int C) {
+  if (nb <= 0 || n <= 0 || C != 128) return 0;
+  const long long rpc = layernorm_mean_rows_per_chunk(n);
+  return (size_t)((n + rpc - 1) / rpc) * (size_t)nb * (size_t)C * sizeof(float);
+}
+
+// the same with out OVERWRITTEN by a fixed-order sum: chunk sums to workspace[chunk][nb][C], then slab_reduce_kernel over the chunks
+int smml_layernorm_fwd_mean_det_f32(const float* x, const float* gamma, const float* beta, float* mean, float* rstd, float* out, int nb,
+                                    long long n, int C, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+  SMML_REQUIRE(workspace && out, "smml_layernorm_fwd_mean_det_f32: null pointer");
+  SMML_REQUIRE(nb > 0 && n > 0 && C == 128, "smml_layernorm_fwd_mean_det_f32: need nb > 0, n > 0 and C = 128");
+  SMML_REQUIRE(workspace_bytes >= smml_layernorm_fwd_mean_det_workspace_bytes(nb, n, C), "smml_layernorm_fwd_mean_det_f32: workspace too small");
+  const long long rpc = layernorm_mean_rows_per_chunk(n), chunks = (n + rpc - 1) / rpc;
+  float* part = chunks == 1 ? out : (float*)workspace;      // a single chunk is the result itself ([1][nb][C]): no second pass
+  if (int rc = layernorm_mean_launch("smml_layernorm_fwd_mean_det_f32", x, gamma, beta, mean, rstd, out, nb, n, C, eps, part, stream)) return rc;
+  SMML_LAUNCH_CHECK("smml_layernorm_fwd_mean_det_f32");
+  if (chunks == 1) return SMML_OK;
+  const long long ncols = (long long)nb * C;
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((ncols + 31) / 32)), dim3(256), 0, (hipStream_t)stream, part, chunks, ncols, out,
+                     out, ncols, 0);
+  SMML_LAUNCH_CHECK("smml_layernorm_fwd_mean_det_f32/reduce");
+  return SMML_OK;
+}
+
+// grid of layernorm_bwd128_kernel: a workgroup takes 8 LN128_BWD_RPT = 16 rows per trip; at most 768 workgroups (the slab rows of the
+// deterministic form's workspace formula in include/smml.h)
+static long long layernorm_bwd128_workgroups(long long R) {
+  const long long nb = (R + 8 * LN128_BWD_RPT - 1) / (8 * LN128_BWD_RPT);
+  return nb < 768 ? nb : 768;
+}
+
 // dgamma / dbeta are accumulated into (callers zero them once; the shared LayerNorm of the two streams adds twice)
 int smml_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd,
                            float* dx, float* dgamma, float* dbeta, long long R, int C, long long rows_per_dy,
@@ -487,8 +630,7 @@ int smml_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, 
   const bool aligned = ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(dy) | reinterpret_cast<size_t>(dx) |
                          reinterpret_cast<size_t>(gamma)) & 15) == 0;
   if (C == 128 && aligned) {
-    const long long nb16 = (R + 15) / 16;
-    hipLaunchKernelGGL(layernorm_bwd128_kernel, dim3((unsigned)(nb16 < 768 ? nb16 : 768)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(layernorm_bwd128_kernel, dim3((unsigned)layernorm_bwd128_workgroups(R)), dim3(256), 0, (hipStream_t)stream,
                        x, dy, gamma, mean, rstd, dx, dgamma, dbeta, R, rows_per_dy, dy_scale, accumulate_dx, (float*)nullptr);
   } else
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)(nblk < 1024 ? nblk : 1024)), dim3(256), 0, (hipStream_t)stream,
@@ -522,7 +664,7 @@ int smml_colsum_f32(const float* x, float* out, int nb, long long R, int C, floa
 // ---- deterministic forms: partial rows to a caller-allocated workspace with plain stores, then slab_reduce_kernel (no float atomics)
 // workgroups of the LayerNorm backward - a function of (R, C) alone: the 128-column kernel's grid at C = 128, else the generic kernel's
 static long long layernorm_bwd_det_workgroups(long long R, int C) {
-  if (C == 128) { const long long nb16 = (R + 15) / 16; return nb16 < 768 ? nb16 : 768; }
+  if (C == 128) return layernorm_bwd128_workgroups(R);
   const long long nblk = (R + 3) / 4;
   return nblk < 1024 ? nblk : 1024;
 }

@@ -111,7 +111,18 @@ class DeformCrossTransMIL(nn.Module):
         (functional.dual_linear_relu) and enters here."""
         omic = omic.float()
         N = path.shape[1]
+        # The plain 2-D branch reads `path` twice (fusion layer, layer3.norm on the key side) and the fusion output h twice (layer3.norm on
+        # the query side, the residual of to_out): each pair of gradients meets in one buffer (functional.GradSum) instead of an ATen add
+        # over three [B, N, C] tensors.  `path` comes from the caller, so the GradSum rides on a private alias of it - every consumer of
+        # the alias is one of the two ops (GradSum's contract); h is made here.
+        side = int(math.ceil(math.sqrt(N)))
+        wrap = bool(getattr(self.args, "wrap_pad_to_square", False)) and side * side != N and getattr(self.args, "grid_hw", None) is None
+        joined = self.args.attn_dim == 2 and not wrap and Fh.GRAD_SUM and torch.is_grad_enabled()
+        if joined and path.requires_grad:
+            path = Fh.grad_sum(path.view_as(path))
         h = self.fusion_layer(path, omic)
+        if joined:
+            Fh.grad_sum(h)
         vgrid = None
         if self.args.attn_dim == 1:
             B = h.shape[0]
@@ -123,9 +134,7 @@ class DeformCrossTransMIL(nn.Module):
             logits = Fh.linear(h, self._fc2.weight, self._fc2.bias)
         elif self.args.attn_dim == 2:
             pth = path
-            side = int(math.ceil(math.sqrt(N)))
-            wrap = bool(getattr(self.args, "wrap_pad_to_square", False)) and side * side != N and getattr(self.args, "grid_hw", None) is None
-            if wrap:                                   # h[:, :add] appended, as mil.py:232-235 does for TransMIL
+            if wrap:                                  # h[:, :add] appended, as mil.py:232-235 does for TransMIL
                 add = side * side - N
                 h = torch.cat((h, h[:, :add]), dim=1)
                 pth = torch.cat((path, path[:, :add]), dim=1)

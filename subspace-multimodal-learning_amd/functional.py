@@ -253,11 +253,67 @@ def colsum(x2d_or_3d: torch.Tensor, scale: float = 1.0, det: Optional[bool] = No
 
 
 # ------------------------------------------------------------------------------------------------
+# A gradient that two kernels produce, summed by the second of them
+# ------------------------------------------------------------------------------------------------
+GRAD_SUM = os.environ.get("SMML_GRAD_SUM", "1") != "0"       # measurement switch, beside deform_attention._GRAD_FORK
+
+
+class GradSum:
+    """A tensor that feeds two of this module's ops - `linear` (as x or as residual) and `layer_norm` - gets two [B, N, C] gradients that
+    autograd would add with an elementwise kernel: two reads and a write of the tensor right after the second producer wrote its half.
+    With a GradSum riding on the tensor (grad_sum below) the producer that runs FIRST parks its gradient here and returns it to autograd as
+    usual; the one that runs SECOND adds its own contribution into that buffer in place - the LayerNorm backward with accumulate_dx = 1,
+    the linear's dX product through the GEMM's residual epilogue (C = 1 * parked + A B, residual aliased to C) - and reports no gradient
+    of its own.  Either way a + b is rounded once in fp32: the bits of the ATen add.  Whichever order autograd picks is handled; a
+    parked gradient is only taken inside the backward pass that parked it (the engine's graph-task id), so partial or repeated backward
+    passes fall back to plain autograd, as does a tensor the second producer cannot add into.
+
+    Contract of the caller that attaches one: every consumer of the tensor is a `linear` / `layer_norm` of this module (a gradient that
+    ATen adds BETWEEN the park and the take would be summed out of place and miss the second half), and the gradient a parking
+    `linear(residual=...)` receives has no other reader (it is the buffer that is added into)."""
+    __slots__ = ("parked", "owner", "task")
+
+    def __init__(self):
+        self.parked = self.owner = self.task = None
+
+    @staticmethod
+    def _task():
+        fn = getattr(torch._C, "_current_graph_task_id", None)
+        t = fn() if fn is not None else -1
+        return None if t < 0 else t
+
+    def take(self, who: str, like: torch.Tensor) -> Optional[torch.Tensor]:
+        """The gradient the OTHER producer parked in this backward pass, if `who` can add into it; the slot is emptied."""
+        t, task = self.parked, self._task()
+        if t is None or self.owner == who or task is None or self.task != task:
+            return None                       # nothing there, or a leftover of this producer / of another pass: park() replaces it
+        self.parked = self.owner = self.task = None
+        ok = t.dtype == torch.float32 and t.is_contiguous() and t.shape == like.shape and t.device == like.device and t.data_ptr() % 16 == 0
+        return t if ok else None
+
+    def park(self, who: str, t: torch.Tensor) -> None:
+        task = self._task()
+        self.parked, self.owner, self.task = (t, who, task) if task is not None else (None, None, None)
+
+
+def grad_sum(t: torch.Tensor) -> torch.Tensor:
+    """Attaches a fresh GradSum to t (see its contract) and returns t; a no-op with the switch off or where t needs no gradient."""
+    if GRAD_SUM and t.requires_grad:
+        t._smml_grad_sum = GradSum()
+    return t
+
+
+def _fork_of(t) -> Optional[GradSum]:
+    return getattr(t, "_smml_grad_sum", None) if (GRAD_SUM and t is not None) else None
+
+
+# ------------------------------------------------------------------------------------------------
 # y = act(x W^T + bias) [+ residual]; bias is [N] or one row per block of `rows_per_bias` rows
 # ------------------------------------------------------------------------------------------------
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, act, rows_per_bias, residual, prec=0):
+    def forward(ctx, x, weight, bias, act, rows_per_bias, residual, prec=0, xfork=None, rfork=None):
+        ctx.xfork, ctx.rfork = xfork, rfork
         x = _c(x); weight = _c(weight)
         ctx.det = DETERMINISTIC
         ctx.prec = 3 if prec == 4 else prec          # fp16 operands are for forward-range values: the gradient products of mode 4 run in bf16
@@ -286,6 +342,8 @@ class _Linear(torch.autograd.Function):
         M = x.numel() // K
         N = weight.shape[0]
         dres = dy if ctx.has_res else None
+        if dres is not None and ctx.rfork is not None and ctx.needs_input_grad[5]:
+            ctx.rfork.park("linear", dres)         # GradSum: the residual's other consumer adds its gradient into this buffer
         if ctx.act == ACT_RELU:
             dpre = torch.empty_like(dy)
             capi.check(capi.lib().smml_relu_bwd_f32(capi.fptr(dy), capi.fptr(y), capi.fptr(dpre), dy.numel(),
@@ -302,8 +360,14 @@ class _Linear(torch.autograd.Function):
         dx = dw = db = None
         with _prec(ctx.prec):
             if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _gemm(dpre, weight, dx, M=M, N=K, K=N, sam=N, sak=1, sbk=K, sbn=1, ldc=K)
+                parked = ctx.xfork.take("linear", x) if ctx.xfork is not None else None
+                if parked is not None:             # GradSum: x's other gradient is there - parked = 1 * parked + dpre W, in place
+                    _gemm(dpre, weight, parked, M=M, N=K, K=N, sam=N, sak=1, sbk=K, sbn=1, ldc=K, residual=parked, ldr=K)
+                else:
+                    dx = torch.empty_like(x)
+                    _gemm(dpre, weight, dx, M=M, N=K, K=N, sam=N, sak=1, sbk=K, sbn=1, ldc=K)
+                    if ctx.xfork is not None:
+                        ctx.xfork.park("linear", dx)
             if ctx.needs_input_grad[1]:
                 dw = torch.empty_like(weight) if ctx.det else _zeros_like(weight)
                 _gemm(dpre, x, dw, M=N, N=K, K=M, sam=1, sak=N, sbk=K, sbn=1, ldc=K, splitk=_splitk_for(N, K, M), det=ctx.det)
@@ -312,7 +376,7 @@ class _Linear(torch.autograd.Function):
                 db = colsum(dpre.reshape(1, M, N), det=ctx.det)[0]
             else:
                 db = colsum(dpre.reshape(M // ctx.rows_per_bias, ctx.rows_per_bias, N), det=ctx.det)
-        return dx, dw, db, None, None, dres, None
+        return dx, dw, db, None, None, dres, None, None, None
 
 
 def linear(x, weight, bias=None, act: int = ACT_NONE, rows_per_bias: int = 1, residual=None, prec: int = 0):
@@ -323,7 +387,8 @@ def linear(x, weight, bias=None, act: int = ACT_NONE, rows_per_bias: int = 1, re
     an odd number of columns raises ValueError)."""
     if act == ACT_TANH_SIGMOID and weight.shape[0] % 2:
         raise ValueError(f"linear: ACT_TANH_SIGMOID splits the output columns in halves, got an odd N = {weight.shape[0]}")
-    return _Linear.apply(x, weight, bias, act, rows_per_bias, residual, prec)
+    # a GradSum riding on x or on the residual (grad_sum): their gradients meet the other consumer's in one buffer
+    return _Linear.apply(x, weight, bias, act, rows_per_bias, residual, prec, _fork_of(x), _fork_of(residual))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1476,21 +1541,25 @@ def grouped_pointwise(x, weight, groups: int = 1):
 # ------------------------------------------------------------------------------------------------
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, token_mean):
+    def forward(ctx, x, gamma, beta, eps, token_mean, fork=None):
+        ctx.fork = fork
         x = _c(x); gamma = _c(gamma); beta = _c(beta)
         Cc = x.shape[-1]
         R = x.numel() // Cc
-        y = torch.empty_like(x)
         mean = torch.empty(R, device=x.device, dtype=torch.float32)
         rstd = torch.empty(R, device=x.device, dtype=torch.float32)
-        capi.check(capi.lib().smml_layernorm_fwd_f32(capi.fptr(x), capi.fptr(gamma), capi.fptr(beta), capi.fptr(y),
-                                                     capi.fptr(mean), capi.fptr(rstd), R, Cc, float(eps),
-                                                     capi.stream()), "layernorm_fwd")
         ctx.token_mean = token_mean
         ctx.det = DETERMINISTIC
         ctx.save_for_backward(x, gamma, mean, rstd)
         if token_mean:
             assert x.dim() == 3
+            if Cc == 128 and _al16(x, gamma, beta):       # the path's width: one pass over x, the normalised tensor is never stored
+                return _layernorm_mean128(x, gamma, beta, mean, rstd, float(eps), ctx.det)
+        y = torch.empty_like(x)
+        capi.check(capi.lib().smml_layernorm_fwd_f32(capi.fptr(x), capi.fptr(gamma), capi.fptr(beta), capi.fptr(y),
+                                                     capi.fptr(mean), capi.fptr(rstd), R, Cc, float(eps),
+                                                     capi.stream()), "layernorm_fwd")
+        if token_mean:
             return colsum(y, 1.0 / x.shape[1], det=ctx.det)
         return y
 
@@ -1500,7 +1569,10 @@ class _LayerNorm(torch.autograd.Function):
         dy = _c(dy)
         Cc = x.shape[-1]
         R = x.numel() // Cc
-        dx = torch.empty_like(x)
+        fork = ctx.fork if ctx.needs_input_grad[0] else None
+        parked = fork.take("norm", x) if fork is not None else None
+        acc = parked is not None                   # GradSum: x's other gradient is there - this one is added into it (accumulate_dx = 1)
+        dx = parked if acc else torch.empty_like(x)
         dg = _zeros_like(gamma)
         db = _zeros_like(gamma)
         rows_per_dy, scale = (x.shape[1], 1.0 / x.shape[1]) if ctx.token_mean else (1, 1.0)
@@ -1509,22 +1581,42 @@ class _LayerNorm(torch.autograd.Function):
             wsb = L.smml_layernorm_bwd_det_workspace_bytes(R, Cc)
             ws = _scratch(wsb, x.device)
             capi.check(L.smml_layernorm_bwd_det_f32(capi.fptr(x), capi.fptr(dy), capi.fptr(gamma), capi.fptr(mean), capi.fptr(rstd),
-                                                    capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc, rows_per_dy, float(scale), 0,
+                                                    capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc, rows_per_dy, float(scale), int(acc),
                                                     capi.fptr(ws), wsb, capi.stream()), "layernorm_bwd (deterministic)")
-            return dx, dg, db, None, None
-        capi.check(capi.lib().smml_layernorm_bwd_f32(capi.fptr(x), capi.fptr(dy), capi.fptr(gamma), capi.fptr(mean),
-                                                     capi.fptr(rstd), capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc,
-                                                     rows_per_dy, float(scale), 0, capi.stream()), "layernorm_bwd")
-        return dx, dg, db, None, None
+        else:
+            capi.check(capi.lib().smml_layernorm_bwd_f32(capi.fptr(x), capi.fptr(dy), capi.fptr(gamma), capi.fptr(mean),
+                                                         capi.fptr(rstd), capi.fptr(dx), capi.fptr(dg), capi.fptr(db), R, Cc,
+                                                         rows_per_dy, float(scale), int(acc), capi.stream()), "layernorm_bwd")
+        if fork is not None and not acc:
+            fork.park("norm", dx)
+        return (None if acc else dx), dg, db, None, None, None
+
+
+def _layernorm_mean128(x, gamma, beta, mean, rstd, eps: float, det: bool) -> torch.Tensor:
+    """x [B, n, 128] -> the mean over tokens of LayerNorm(x) [B, 128]; fills mean / rstd (include/smml.h smml_layernorm_fwd_mean_f32)"""
+    L = capi.lib()
+    nb, n, Cc = x.shape
+    if det:
+        out = torch.empty(nb, Cc, device=x.device, dtype=torch.float32)
+        wsb = L.smml_layernorm_fwd_mean_det_workspace_bytes(nb, n, Cc)
+        ws = _scratch(wsb, x.device)
+        capi.check(L.smml_layernorm_fwd_mean_det_f32(capi.fptr(x), capi.fptr(gamma), capi.fptr(beta), capi.fptr(mean), capi.fptr(rstd),
+                                                     capi.fptr(out), nb, n, Cc, eps, capi.fptr(ws), wsb, capi.stream()),
+                   "layernorm_fwd_mean (deterministic)")
+        return out
+    out = _ZEROS.zeros((nb, Cc), x.device)
+    capi.check(L.smml_layernorm_fwd_mean_f32(capi.fptr(x), capi.fptr(gamma), capi.fptr(beta), capi.fptr(mean), capi.fptr(rstd),
+                                             capi.fptr(out), nb, n, Cc, eps, capi.stream()), "layernorm_fwd_mean")
+    return out
 
 
 def layer_norm(x, gamma, beta, eps: float = 1e-5):
-    return _LayerNorm.apply(x, gamma, beta, eps, False)
+    return _LayerNorm.apply(x, gamma, beta, eps, False, _fork_of(x))       # a GradSum riding on x (grad_sum)
 
 
 def layer_norm_token_mean(x, gamma, beta, eps: float = 1e-5):
     """mean over tokens of LayerNorm(x): x [B, n, C] -> [B, C]."""
-    return _LayerNorm.apply(x, gamma, beta, eps, True)
+    return _LayerNorm.apply(x, gamma, beta, eps, True, None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2396,7 +2488,9 @@ class _TileTokens(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, n):
         ctx.det = DETERMINISTIC
-        return v.unsqueeze(1).repeat(1, n, 1)
+        # the broadcast view, not a copy (41 MB per 8-bag step that BatchLoss never reads: it takes _smml_compact): equal values; whoever
+        # needs the rows in memory (reshape, .contiguous(), a kernel's _c) materialises them then
+        return v.unsqueeze(1).expand(-1, n, -1)
 
     @staticmethod
     def backward(ctx, dy):
@@ -2404,7 +2498,7 @@ class _TileTokens(torch.autograd.Function):
 
 
 def tile_tokens(v, n: int):
-    """v [B, C] -> [B, n, C] (values of v.unsqueeze(1).repeat(1, n, 1)); backward is a column sum.
+    """v [B, C] -> [B, n, C] (values of v.unsqueeze(1).repeat(1, n, 1), as a broadcast view); backward is a column sum.
     The result carries the un-tiled vector as `_smml_compact`: BatchLoss uses it to gather [B, C] instead of the
     n-times larger tile across ranks (the Gram of a tile is n x the Gram of the vector, and the row normalisation
     that follows cancels the factor)."""
