@@ -702,6 +702,36 @@ int smml_fewq_attn_bwd_f32(const float* u, const float* x, const float* y, const
                            long long dy_batch_stride, long long dy_row_stride, int splits, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Few-key co-attention (the same module with a bag of L queries over S <= 8 keys: CMTA's P_in_G_Att), the dual problem: the projections fold
+ * onto the keys.  With k^ = key Wk^T + bk and v^ = value Wv^T + bv, u = scaling k^ Wq, c = scaling k^ . bq and w = v^ Wo^T + bo (formed by the
+ * caller, [B S, E]-sized):
+ *   raw[b, l, j] = x[b, l, :] . u[b, j, :] + c[b, j]      out[b, l, :] = sum_j softmax_j(raw[b, l, :])[j] w[b, j, :]
+ * and out IS the module's output (bo folds into w because the weights of a row sum to one).  One streaming pass over the rows of x: S dot
+ * products, a softmax over S numbers and a weighted sum of S rows per row; no sum crosses rows in the forward.
+ *   x [B, L, Eq]: unit column stride, rows x_row_stride and bags x_batch_stride floats apart (multiples of 4; a slice or a sequence-first
+ *   tensor is read in place)   u [B, S, Eq]   c [B, S]   w [B, S, Eo]   out [B, L, Eo]   raw [B, L, S]   dense.
+ *   key_padding_mask [B, S] bytes (non-zero: the key is masked, its raw score is -inf) or null; a bag whose keys are ALL masked gives NaN, as
+ *   in the reference.  1 <= S <= 8, Eq and Eo multiples of 64 up to 512, any L >= 1 (anything else is an error, nothing is launched); x, u,
+ *   w, out, dout, dx and the workspace 16-byte aligned.
+ * splits: as for smml_fewq_attn_fwd_f32 (0 = about 1024 workgroups over the B bags, no split under 64 rows, whole tiles of 16 rows); the
+ * forward's result does not depend on it and its workspace is empty (the size function and the two arguments mirror the few-query entry).
+ * Backward, for dout (rows of width Eo, strides of their own), the saved raw and optionally draw [B, L, S] (the gradient of the raw scores;
+ * null: none arrived): p = softmax(raw), dp = dout . w_j, g = p (dp - sum_j p dp) + draw (0 at masked keys);
+ *   dx [B, L, Eq] = sum_j g u_j (strides of its own; null: nothing is formed)   du [B, S, Eq] = sum_l g x_l   dc [B, S] = sum_l g
+ *   dw [B, S, Eo] = sum_l p dout_l      all overwritten.
+ * The workgroups' du / dc / dw partials go to the workspace and are added in ascending split order: no float atomics, the result is a
+ * function of the inputs and `splits` alone. */
+size_t smml_fewk_attn_fwd_workspace_bytes(int B, int L, int S, int Eo, int splits);
+int smml_fewk_attn_fwd_f32(const float* x, const float* u, const float* c, const float* w, const unsigned char* key_padding_mask, float* out,
+                           float* raw, void* workspace, size_t workspace_bytes, int B, int L, int S, int Eq, int Eo, long long x_batch_stride,
+                           long long x_row_stride, int splits, void* stream);
+size_t smml_fewk_attn_bwd_workspace_bytes(int B, int L, int S, int Eq, int Eo, int splits);
+int smml_fewk_attn_bwd_f32(const float* x, const float* u, const float* w, const float* raw, const float* dout, const float* draw, float* dx,
+                           float* du, float* dc, float* dw, void* workspace, size_t workspace_bytes, int B, int L, int S, int Eq, int Eo,
+                           long long x_batch_stride, long long x_row_stride, long long dout_batch_stride, long long dout_row_stride,
+                           long long dx_batch_stride, long long dx_row_stride, int splits, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sets of at most 8 tokens (MCAT_Surv after its co-attention, models/model.py:589-651: nn.TransformerEncoder with 8 heads over the 4 genomic
  * tokens, then Attn_Net_Gated + softmax + bmm).  A token set is a few KB and its cost is launches: every entry point below is ONE launch, with no
  * workspace and no float atomics - the results are a function of the inputs alone.

@@ -99,9 +99,13 @@ class CMTA(nn.Module):
         self.P_in_G_Att = MultiheadAttention(embed_dim=256, num_heads=1)
         self.G_in_P_Att = MultiheadAttention(embed_dim=256, num_heads=1)
         # extension key: coattn_fused (absent / false: the composed path) - the 4 genomic queries over the bag take the few-query kernels
-        # (coattention.MultiheadAttention.fused_few_query).  P_in_G_Att, many queries over 4 keys, is the dual problem and stays composed.
+        # (coattention.MultiheadAttention.fused_few_query).  Extension key: coattn_fused_few_key (absent / false: composed) - P_in_G_Att, every
+        # bag token over the 4 genomic keys, takes the few-key kernels (fused_few_key).  With both the block touches the bag only through
+        # streaming kernels.
         if getattr(args, "coattn_fused", False):
             self.G_in_P_Att.fused_few_query = True
+        if getattr(args, "coattn_fused_few_key", False):
+            self.P_in_G_Att.fused_few_key = True
         self.genomics_encoder = Transformer_G(feature_dim=hidden[-1], compute_dtype=cd)
         self.genomics_decoder = Transformer_G(feature_dim=hidden[-1], compute_dtype=cd)
         if self.fusion == 'concat':

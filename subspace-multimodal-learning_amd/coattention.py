@@ -10,7 +10,9 @@ the reference uses them.  The reference's `torch.equal(query, key)` host sync (:
 algebraically identical in-projection paths and is not reproduced.
 
 Extension, off by default: `fused_few_query = True` routes one-head calls with at most 8 queries (G_in_P_Att: 4 genomic queries over the
-bag) through the folded form on csrc/fewq_attn.hip - one streaming pass over the bag, no projected key / value tensors."""
+bag) through the folded form on csrc/fewq_attn.hip - one streaming pass over the bag, no projected key / value tensors.
+`fused_few_key = True` does the same for the dual call, a bag of queries over at most 8 keys (P_in_G_Att: every bag token over the 4 genomic
+tokens), on csrc/fewk_attn.hip: the query and out projections fold onto the keys and the bag is read once and written once."""
 from __future__ import annotations
 
 import torch
@@ -59,6 +61,10 @@ class MultiheadAttention(nn.Module):
         # projected key / value tensor is formed.  Plain attributes, not parameters or buffers: the state_dict is unchanged.
         self.fused_few_query = False
         self.fewq_splits = None               # pieces a bag's rows are cut into on that path (None: the library chooses; tests force ragged ones)
+        # the dual extension: True sends calls that coattn_few_key_why() clears - one head, at most 8 keys, no attn_mask, no bias_kv /
+        # zero_attn rows, dropout inactive - through the folded form on csrc/fewk_attn.hip.  Asked after the few-query route.
+        self.fused_few_key = False
+        self.fewk_splits = None               # as fewq_splits, for the few-key path
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -90,6 +96,10 @@ class MultiheadAttention(nn.Module):
                           add_bias_kv=self.bias_k is not None, add_zero_attn=self.add_zero_attn,
                           dropout_active=self.training and self.dropout > 0, fused=self.fused_few_query) == "fewq":
             return self._forward_few_query(query, key, value, key_padding_mask, need_weights, need_raw, (wq, wk, wv), (bq, bk, bv), scaling)
+        if self.fused_few_key and Fh.coattn_few_key_why(S=S, heads=h, Eq=E, attn_mask=attn_mask is not None, add_bias_kv=self.bias_k is not None,
+                                                        add_zero_attn=self.add_zero_attn, dropout_active=self.training and self.dropout > 0,
+                                                        fused=True) is None:
+            return self._forward_few_key(query, key, value, key_padding_mask, need_weights, need_raw, (wq, wk, wv), (bq, bk, bv), scaling)
 
         def heads_first(t, n):          # [B, n, E] -> [B, h, n, hd]
             return t.reshape(B, 1, n, E) if h == 1 else t.reshape(B, n, h, hd).permute(0, 2, 1, 3)
@@ -161,3 +171,22 @@ class MultiheadAttention(nn.Module):
         if need_raw:
             return out, raw.unsqueeze(1)                                              # [B, 1, L, S], masked entries -inf
         return out, torch.exp(raw - lse.unsqueeze(-1))                                # the softmax [B, L, S] (one head: the head average is itself)
+
+    def _forward_few_key(self, query, key, value, key_padding_mask, need_weights, need_raw, w, b, scaling):
+        """The dual folded form: raw = x_l . (s Wq^T k^_j) + s bq . k^_j and out = sum_j softmax(raw) (Wo v^_j + bo) with k^ = Wk key + bk,
+        v^ = Wv value + bv.  The bag-sized work is the core of functional.few_key_attention; the [B S, E]-sized products around it are GEMM
+        launches inside the same autograd node (functional.coattn_few_key).  Several heads would fold the same way, as h S virtual keys
+        with a softmax per group of S; only one head is wired."""
+        (wq, wk, wv), (bq, bk, bv) = w, b
+        B, S = query.shape[1], key.shape[0]
+        if key_padding_mask is not None and tuple(key_padding_mask.shape) != (B, S):
+            raise RuntimeError("key_padding_mask must be [batch, source length]")
+        out, raw = Fh.coattn_few_key(query.transpose(0, 1), key.transpose(0, 1), value.transpose(0, 1), wq, bq, wk, bk, wv, bv,
+                                     self.out_proj.weight, self.out_proj.bias, scaling=scaling, key_padding_mask=key_padding_mask,
+                                     splits=self.fewk_splits)
+        out = out.transpose(0, 1)
+        if not need_weights:
+            return out, None
+        if need_raw:
+            return out, raw.unsqueeze(1)                                              # [B, 1, L, S], masked entries -inf
+        return out, torch.softmax(raw, dim=-1)                                        # [B, L, S] (one head: the head average is itself)

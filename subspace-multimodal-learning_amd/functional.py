@@ -935,6 +935,214 @@ def coattn_few_query(q, x, y, wq, bq, wk, bk, wv, bv, wo, bo, *, scaling: float,
 
 
 # ------------------------------------------------------------------------------------------------
+# few-key co-attention (the same module with a bag of queries over S <= 8 keys: CMTA's P_in_G_Att; csrc/fewk_attn.hip), the dual fold: with
+# k^ = key Wk^T + bk and v^ = value Wv^T + bv, raw = x_l . u_j + c_j for u = s k^ Wq, c = s k^ . bq and the output is sum_j softmax(raw) w_j
+# for w = v^ Wo^T + bo (bo folds in: the weights of a row sum to one) - the query and out projections become [B S, E]-sized products and the
+# bag streams once through few_key_attention.  The launches take their arguments by the header's parameter names (capi.call); the key sets:
+# ------------------------------------------------------------------------------------------------
+FEWK_MAX_S, FEWK_MAX_E = 8, 512
+_FEWK = "x u w B L S Eq Eo x_batch_stride x_row_stride splits stream workspace workspace_bytes "
+FEWK_FWD_KEYS = frozenset((_FEWK + "c key_padding_mask out raw").split())
+FEWK_BWD_KEYS = frozenset((_FEWK + "raw dout draw dx du dc dw dout_batch_stride dout_row_stride dx_batch_stride dx_row_stride").split())
+
+
+def _fewk_width_ok(E: int) -> bool:
+    return 0 < E <= FEWK_MAX_E and E % 64 == 0
+
+
+def coattn_few_key_why(*, S: int, heads: int, Eq: int, attn_mask: bool = False, add_bias_kv: bool = False, add_zero_attn: bool = False,
+                       dropout_active: bool = False, fused: bool = True) -> Optional[str]:
+    """Why a MultiheadAttention call with S keys, `heads` heads and embedding width Eq (the width of the queries and of the output) stays
+    on the composed path (two bag-sized projections, matmul4, softmax_rows, matmul4); None: it takes the few-key kernels.  Same contract
+    as coattn_why, which is asked first: no GPU work."""
+    if not fused:
+        return "fused_few_key is off (the default)"
+    if heads != 1:
+        return f"{heads} heads (the few-key kernels are one-head)"
+    if not 1 <= S <= FEWK_MAX_S:
+        return f"{S} keys (at most {FEWK_MAX_S})"
+    if attn_mask:
+        return "an attn_mask (only key_padding_mask is fused)"
+    if add_bias_kv:
+        return "add_bias_kv (a learned key / value row outside the key set)"
+    if add_zero_attn:
+        return "add_zero_attn (a zero key / value row outside the key set)"
+    if dropout_active:
+        return "active attention dropout"
+    if not _fewk_width_ok(Eq):
+        return f"embedding width {Eq} (a multiple of 64 up to {FEWK_MAX_E})"
+    return None
+
+
+def _fewk_check(x, u, c, w):
+    """Shapes the few-key kernels are built for (include/smml.h); raises ValueError before anything is launched."""
+    if x.dim() != 3 or u.dim() != 3 or w.dim() != 3 or c.dim() != 2:
+        raise ValueError(f"few_key_attention: need x [B, L, Eq], u [B, S, Eq], c [B, S], w [B, S, Eo], got {tuple(x.shape)}, {tuple(u.shape)}, "
+                         f"{tuple(c.shape)}, {tuple(w.shape)}")
+    B, L, Eq = x.shape
+    S, Eo = u.shape[1], w.shape[2]
+    if tuple(u.shape) != (B, S, Eq) or tuple(c.shape) != (B, S) or tuple(w.shape[:2]) != (B, S):
+        raise ValueError(f"few_key_attention: x {tuple(x.shape)}, u {tuple(u.shape)}, c {tuple(c.shape)} and w {tuple(w.shape)} do not "
+                         "describe one problem")
+    if B < 1 or L < 1:
+        raise ValueError(f"few_key_attention: empty bag ({tuple(x.shape)})")
+    if not 1 <= S <= FEWK_MAX_S:
+        raise ValueError(f"few_key_attention: between 1 and {FEWK_MAX_S} keys, got {S}")
+    if not _fewk_width_ok(Eq) or not _fewk_width_ok(Eo):
+        raise ValueError(f"few_key_attention: the query and output widths must be multiples of 64 up to {FEWK_MAX_E}, got {Eq} and {Eo}")
+    return B, L, S, Eq, Eo
+
+
+def _fewk_mask(name: str, key_padding_mask, B: int, S: int):
+    if key_padding_mask is None:
+        return None
+    mask = key_padding_mask.to(torch.bool).contiguous().view(torch.uint8)
+    if tuple(mask.shape) != (B, S):
+        raise ValueError(f"{name}: key_padding_mask must be [B, S] = {(B, S)}, got {tuple(mask.shape)}")
+    return mask
+
+
+def _fewk_fwd(x, u, c, w, mask, splits: int):
+    """One launch of the forward core on checked operands (u, c, w dense; x as _rows leaves it) -> (out [B, L, Eo], raw [B, L, S])"""
+    B, L, Eq = x.shape
+    S, Eo = u.shape[1], w.shape[2]
+    out = torch.empty(B, L, Eo, device=x.device, dtype=torch.float32)
+    raw = torch.empty(B, L, S, device=x.device, dtype=torch.float32)
+    ns = dict(x=_rows_ptr(x), u=u, c=c, w=w, key_padding_mask=mask, out=out, raw=raw, workspace=None, workspace_bytes=0, B=B, L=L, S=S,
+              Eq=Eq, Eo=Eo, x_batch_stride=_bs(x), x_row_stride=x.stride(1), splits=splits, stream=capi.stream())
+    capi.check(capi.call("smml_fewk_attn_fwd_f32", ns, FEWK_FWD_KEYS), "fewk_attn_fwd")
+    return out, raw
+
+
+def _fewk_bwd(x, u, w, raw, dout, draw, want_dx: bool, splits: int):
+    """One launch of the backward core -> (dx or None, du, dc, dw); dout / draw may be None (no gradient arrived for that output)."""
+    B, L, Eq = x.shape
+    S, Eo = u.shape[1], w.shape[2]
+    dout = _rows(dout) if dout is not None else torch.zeros(B, L, Eo, device=x.device, dtype=torch.float32)
+    draw = _c(draw) if draw is not None else None
+    dx = _grad_rows(x) if want_dx else None
+    du, dw = torch.empty_like(u), torch.empty_like(w)
+    dc = torch.empty(B, S, device=x.device, dtype=torch.float32)
+    dims = dict(B=B, L=L, S=S, Eq=Eq, Eo=Eo, splits=splits)
+    wsb = capi.call("smml_fewk_attn_bwd_workspace_bytes", dims)
+    ws = _scratch(wsb, x.device)
+    ns = dict(dims, x=_rows_ptr(x), u=u, w=w, raw=raw, dout=_rows_ptr(dout), draw=draw, dx=_rows_ptr(dx), du=du, dc=dc, dw=dw, workspace=ws,
+              workspace_bytes=wsb, x_batch_stride=_bs(x), x_row_stride=x.stride(1), dout_batch_stride=_bs(dout), dout_row_stride=dout.stride(1),
+              dx_batch_stride=_bs(dx) if want_dx else 0, dx_row_stride=dx.stride(1) if want_dx else 0, stream=capi.stream())
+    capi.check(capi.call("smml_fewk_attn_bwd_f32", ns, FEWK_BWD_KEYS), "fewk_attn_bwd")
+    return dx, du, dc, dw
+
+
+class _FewKeyAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, u, c, w, mask, splits):
+        _fewk_check(x, u, c, w)
+        ctx.set_materialize_grads(False)
+        x = _rows(x); u = _c(u); c = _c(c); w = _c(w)
+        ctx.splits = int(splits or 0)
+        out, raw = _fewk_fwd(x, u, c, w, mask, ctx.splits)
+        ctx.save_for_backward(x, u, w, raw)
+        return out, raw
+
+    @staticmethod
+    def backward(ctx, dout, draw):
+        x, u, w, raw = ctx.saved_tensors
+        dx, du, dc, dw = _fewk_bwd(x, u, w, raw, dout, draw, ctx.needs_input_grad[0], ctx.splits)
+        return dx, du, dc, dw, None, None
+
+
+def few_key_attention(x, u, c, w, *, key_padding_mask=None, splits=None):
+    """(out [B, L, Eo], raw [B, L, S]) with raw[b, l, j] = x[b, l] . u[b, j] + c[b, j] and out = sum_j softmax_j(raw) w[b, j], for a bag of
+    rows x [B, L, Eq] over S <= 8 keys u [B, S, Eq], c [B, S] with output rows w [B, S, Eo] - one streaming pass over the bag: every row of x
+    is read once, every row of out written once.  Eq and Eo multiples of 64 up to 512, any L >= 1; other shapes raise ValueError before
+    anything is launched.  x is read in place when its columns are contiguous (a slice of a longer bag, the transpose of a sequence-first
+    tensor).
+    key_padding_mask [B, S] bool: masked keys get raw = -inf, weight 0 and zero gradient rows du, dc, dw; a bag with every key masked gives
+    NaN, as the reference does (not checked: that would be a host sync).
+    Both outputs are differentiable; u, c and w receive gradients, x only where it requires one (no buffer is written otherwise), in x's
+    own layout where that is dense.
+    splits: how many pieces a bag's rows are cut into (None: chosen by the library so that B x splits fills the chip); the gradients are
+    a function of the inputs and this number alone, the outputs of the inputs alone - the same under functional.deterministic().
+    Several heads would fold as h S virtual keys with a softmax per group of S; only one head is built."""
+    B, _, S, _, _ = _fewk_check(x, u, c, w)
+    return _FewKeyAttention.apply(x, u, c, w, _fewk_mask("few_key_attention", key_padding_mask, B, S), splits)
+
+
+class _CoattnFewKey(torch.autograd.Function):
+    """The whole folded co-attention as ONE autograd node, as _CoattnFewQuery is for the dual problem: the [B S, E]-sized products around
+    the core are the same smml_gemm launches (k^ = k Wk^T + bk; u = s k^ Wq, c = s k^ . bq with the scaling s as the products' alpha;
+    v^ = v Wv^T + bv; w = v^ Wo^T + bo) and their gradients are formed as _Linear.backward forms them.  v = None: the values are the keys
+    (one tensor, one gradient dk + dv)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, wq, bq, wk, bk, wv, bv, wo, bo, mask, splits, scaling):
+        B, S, _ = k.shape
+        ctx.set_materialize_grads(False)
+        ctx.det = DETERMINISTIC
+        ctx.splits, ctx.scaling, ctx.same = int(splits or 0), float(scaling), v is None
+        ctx.shapes = tuple(None if b is None else b.shape for b in (bq, bk, bv, bo))
+        k2 = _c(k).reshape(B * S, -1)
+        v2 = k2 if v is None else _c(v).reshape(B * S, -1)
+        wq, wk, wv, wo = _c(wq), _c(wk), _c(wv), _c(wo)
+        bqc, bkc, bvc, boc = (None if b is None else _c(b).reshape(-1) for b in (bq, bk, bv, bo))
+        E = wq.shape[0]
+        x = _rows(q)
+        kh = _lin(k2, wk, bkc)
+        u = _mat(kh, wq, alpha=ctx.scaling).view(B, S, -1)
+        c = _lin(kh, bqc.view(1, E), alpha=ctx.scaling).view(B, S) if bqc is not None else torch.zeros(B, S, device=q.device)
+        vh = _lin(v2, wv, bvc)
+        w = _lin(vh, wo, boc).view(B, S, -1)
+        out, raw = _fewk_fwd(x, u, c, w, mask, ctx.splits)
+        ctx.save_for_backward(x, k2, None if ctx.same else v2, kh, vh, u, w, raw, wq, bqc, wk, wv, wo)
+        return out, raw
+
+    @staticmethod
+    def backward(ctx, dout, draw):
+        x, k2, v2, kh, vh, u, w, raw, wq, bq, wk, wv, wo = ctx.saved_tensors
+        B, S, _ = u.shape
+        R, s, det = B * S, ctx.scaling, ctx.det
+        col = lambda g, shape: None if shape is None else colsum(g.reshape(1, R, -1), det=det)[0].view(shape)      # noqa: E731
+        dx, du, dc, dw = _fewk_bwd(x, u, w, raw, dout, draw, ctx.needs_input_grad[0], ctx.splits)
+        du2, dc2, dw2 = du.view(R, -1), dc.view(R, 1), dw.view(R, -1)
+        dvh = _mat(dw2, wo)
+        dwo, dbo = _wgrad(dw2, vh, det), col(dw2, ctx.shapes[3])
+        dwv, dbv = _wgrad(dvh, k2 if ctx.same else v2, det), col(dvh, ctx.shapes[2])
+        dkh = _lin(du2, wq, alpha=s)                                        # s du Wq^T ...
+        dwq = _wgrad(kh, du2, det, alpha=s)
+        dbq = None
+        if bq is not None:
+            dkh.addcmul_(dc2, bq.view(1, -1), value=s)                      # ... + s dc bq^T, [B S, E]-sized
+            dbq = _wgrad(kh, dc2, det, alpha=s).view(ctx.shapes[0])
+        dwk, dbk = _wgrad(dkh, k2, det), col(dkh, ctx.shapes[1])
+        need_k, need_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and not ctx.same
+        dk = _mat(dkh, wk).view(B, S, -1) if need_k else None
+        dv = _mat(dvh, wv).view(B, S, -1) if need_v or (need_k and ctx.same) else None
+        if ctx.same and need_k:
+            dk, dv = dk.add_(dv), None                                      # one tensor: its gradient is dk + dv
+        return dx, dk, dv, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, None, None, None
+
+
+def coattn_few_key(q, k, v, wq, bq, wk, bk, wv, bv, wo, bo, *, scaling: float, key_padding_mask=None, splits=None):
+    """(out [B, L, E], raw [B, L, S]) of one-head co-attention in the few-key folded form, batch first: q [B, L, E] a bag of queries,
+    k [B, S, Ek] keys, v [B, S, Ev] values (None, k itself or another view of k's base over the same memory: the values are the keys),
+    Wq [E, E], Wk [E, Ek], Wv [E, Ev], Wo [Eo, E] and their biases (any may be None).  The bag-sized work is few_key_attention's core; shapes,
+    masks, `splits` and determinism as there.  Both outputs and every input are differentiable; q receives a gradient only where it
+    requires one."""
+    same = _same_rows(k, v)
+    if q.dim() != 3 or k.dim() != 3 or wq.dim() != 2 or wo.dim() != 2 or wq.shape[1] != q.shape[-1] or wk.shape[0] != wq.shape[0] or \
+            wv.shape[0] != wo.shape[1] or wk.shape[1] != k.shape[-1]:
+        raise ValueError(f"coattn_few_key: need q [B, L, E], k [B, S, Ek], Wq [E, E], Wk [E, Ek], Wv [E, Ev], Wo [Eo, E], got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(wq.shape)}, {tuple(wk.shape)}, {tuple(wv.shape)}, {tuple(wo.shape)}")
+    B, S = k.shape[:2]
+    vv = k if same else v
+    if tuple(vv.shape[:2]) != (B, S) or wv.shape[1] != vv.shape[-1]:
+        raise ValueError(f"coattn_few_key: Wv {tuple(wv.shape)} and the keys {tuple(k.shape)} do not take values of shape {tuple(vv.shape)}")
+    _fewk_check(q, torch.empty(B, S, q.shape[-1], device="meta"), torch.empty(B, S, device="meta"), torch.empty(B, S, wo.shape[0], device="meta"))
+    mask = _fewk_mask("coattn_few_key", key_padding_mask, B, S)
+    return _CoattnFewKey.apply(q, k, None if same else v, wq, bq, wk, bk, wv, bv, wo, bo, mask, splits, scaling)
+
+
+# ------------------------------------------------------------------------------------------------
 # sets of at most 8 tokens (MCAT_Surv after its co-attention, models/model.py:589-651; csrc/token_set.hip): multi-head self-attention from
 # the packed projection and gated attention pooling WITH the gradient of the pooled rows - one launch per direction each, no workspace,
 # no float atomics.  The launches take their arguments by the header's parameter names (capi.call); the key sets:
