@@ -773,6 +773,40 @@ int smml_token_pool_gated_bwd_f32(const float* x, const float* h2, const float* 
                                   float* dw, float* db, int B, int T, int E, int D, long long x_batch_stride, long long x_token_stride,
                                   long long dx_batch_stride, long long dx_token_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Self-normalising encoder stacks (SNN_Block, models/mcat_utils.py:81-95: the sig_networks of MCAT_Surv and CMTA; MaxNet's encoder,
+ * models/model.py:142-187): G independent networks (1 <= G <= 8) of `depth` layers each (1 <= depth <= 4, the same for every network), all of
+ * them in ONE forward launch and TWO backward launches.  Layer l = 1 .. depth of network g:
+ *   z_l = a_{l-1} W_l^T + b_l        W_l [N_l, K_l] row-major (nn.Linear's), K_l = N_{l-1}, a_0 = x_g [B, K_0]
+ *   e_l = z_l > 0 ? z_l : expm1(z_l)                                                     (ELU, alpha = 1)
+ *   a_l = e_l (keep null) or A keep e_l + A alpha' (keep - 1) + A alpha' p               (torch's AlphaDropout for the 0 / 1 tensor keep;
+ *                                                                                         alpha' = 1.7580993408473766, A = ((alpha'^2 p + 1)(1 - p))^-1/2)
+ *   out_g [B, N_depth] = final_relu ? max(a_depth, 0) : a_depth
+ * 1 <= K_0 <= 2048, 1 <= N_l <= 256, any B >= 1, no width needs to be a multiple of anything and no pointer an alignment (anything else is an
+ * error, nothing is launched).
+ * The per-network and per-layer device addresses travel as HOST arrays of 64-bit addresses, widths, strides and offsets as HOST arrays; the
+ * entry point reads them during the call into the kernels' by-value argument - no device allocation, no copy, nothing is retained:
+ *   x [G]: the base of network g's input; its rows start x_col_offset[g] floats into rows x_row_stride[g] floats apart (unit column stride): a
+ *          column range of a wider [B, sum K] tensor is read in place
+ *   W, b [G depth]: entry g depth + l - 1 is W_l, b_l of network g          widths [G (depth + 1)]: K_0, N_1 .. N_depth of network g
+ *   out [G]: dense [B, N_depth] each (they may be the slices of one [G, B, N] buffer)
+ * acts (device, B sum_{g, l} N_l floats): every e_l, dense [B, N_l] blocks in the order g = 0 .. G - 1, within g l = 1 .. depth; keep (device,
+ * the same layout, 0 or 1; required with p > 0, null with p = 0) and the backward's scratch dz (device, the same layout and size, every
+ * element written: dz_l = da_l . A keep . (e_l > 0 ? 1 : e_l + 1)) share it.
+ * Backward, for dout [G] (dense [B, N_depth] each; 0: no gradient arrived for that network): the final ReLU's mask is taken from out (needed
+ * with final_relu only), da_{l-1} = dz_l W_l;
+ *   dW [G depth]: dW_l [N_l, K_l] = dz_l^T a_{l-1}      db [G depth]: db_l [N_l] = sum_b dz_l      one separately allocated buffer per parameter,
+ *   dx [G] (the table may be null, an entry 0: not formed): dense [B, K_0]
+ * all overwritten; each element has one owner, which adds over the rows b = 0 .. B - 1 in that order (dW, db) or over n ascending (da, dx): no
+ * float atomics, the results are a function of the inputs alone. */
+int smml_snn_stack_fwd_f32(const unsigned long long* x, const long long* x_row_stride, const long long* x_col_offset, const unsigned long long* W,
+                           const unsigned long long* b, const int* widths, const float* keep, float* acts, const unsigned long long* out, int G,
+                           int depth, int B, float p, int final_relu, void* stream);
+int smml_snn_stack_bwd_f32(const unsigned long long* x, const long long* x_row_stride, const long long* x_col_offset, const unsigned long long* W,
+                           const int* widths, const float* keep, const float* acts, const unsigned long long* out, const unsigned long long* dout,
+                           float* dz, const unsigned long long* dW, const unsigned long long* db, const unsigned long long* dx, int G, int depth,
+                           int B, float p, int final_relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@
 
 Same constructors, forward kwargs, return tuples and parameter names (checkpoint format).  TransLayer / PPEG /
 NystromAttention / MultiheadAttention are the package's HIP-backed modules; every nn.Linear runs through smml_gemm.
-What stays in ATen: ELU / AlphaDropout / Dropout on [B, <= 256] or [B, n, 256] activations, cat / stack, sigmoid, cumprod.
+What stays in ATen: ELU / AlphaDropout of the sig_networks (unless the extension key `snn_fused` sends all of them through ONE
+functional.snn_stack call, csrc/snn_stack.hip), Dropout on [B, n, 256] activations, cat / stack, sigmoid, cumprod.
 The reference's hard `.cuda()` calls (cmta_utils.py:914,940) become `.to(features.device)`."""
 from __future__ import annotations
 
@@ -73,6 +74,29 @@ def _snn(seq: nn.Sequential, x):
     return x
 
 
+def _snn_fused(nets, xs, training: bool, *, final_relu: bool = False, stacked: bool = False):
+    """Every encoder of `nets` (sequences of Linear + ELU + AlphaDropout blocks) on its input of `xs` in ONE functional.snn_stack call, or
+    None where functional.snn_why names a reason against it (the caller then runs its composed form).  The rates are read from the
+    AlphaDropout modules now.  In train mode the 0 / 1 multipliers of all layers of all networks come from ONE draw (bernoulli_ on one
+    flat tensor): reproducible under torch.manual_seed, but not the random stream of the composed form, which draws once per layer."""
+    lins = [[blk[0] for blk in net] for net in nets]
+    widths = [[ls[0].in_features] + [lin.out_features for lin in ls] for ls in lins]
+    rates = [float(blk[2].p) for net in nets for blk in net] if training else (0.0,)
+    if Fh.snn_why(widths, rates=rates, dtypes=[t.dtype for ls in lins for lin in ls for t in (lin.weight, lin.bias)]) is not None:
+        return None
+    p = rates[0]
+    keep = Fh.snn_draw_keep(xs[0].shape[0], widths, p, xs[0].device) if p > 0 else None
+    return Fh.snn_stack(xs, [[lin.weight for lin in ls] for ls in lins], [[lin.bias for lin in ls] for ls in lins], p=p, keep=keep,
+                        final_relu=final_relu, stacked=stacked)
+
+
+def _sig_tokens(sig_networks, x_omic, training: bool, fused: bool):
+    """[G, B, 256]: every signature network on its columns of x_omic (x_omic: the list of column views) - one fused call that reads the
+    views in place (`snn_fused`), or the composed encoders and a stack"""
+    h = _snn_fused(sig_networks, [x.float() for x in x_omic], training, stacked=True) if fused else None
+    return h if h is not None else torch.stack([_snn(sig_networks[i], x.float()) for i, x in enumerate(x_omic)])
+
+
 class CMTA(nn.Module):
     def __init__(self, args, fusion='concat', omic_sizes=[100, 100, 100, 131], n_classes=4, model_size_wsi: str = 'small',
                  model_size_omic: str = 'small', dropout=0.25):
@@ -106,6 +130,9 @@ class CMTA(nn.Module):
             self.G_in_P_Att.fused_few_query = True
         if getattr(args, "coattn_fused_few_key", False):
             self.P_in_G_Att.fused_few_key = True
+        # extension key: snn_fused (absent / false: linear, ELU and AlphaDropout per layer) - all sig_networks in one functional.snn_stack call
+        # on the column views of x_omic (_snn_fused: one draw of the dropout multipliers per step, a random stream of its own)
+        self.snn_fused = bool(getattr(args, "snn_fused", False))
         self.genomics_encoder = Transformer_G(feature_dim=hidden[-1], compute_dtype=cd)
         self.genomics_decoder = Transformer_G(feature_dim=hidden[-1], compute_dtype=cd)
         if self.fusion == 'concat':
@@ -123,8 +150,7 @@ class CMTA(nn.Module):
         x_omic = [x_omic_all[:, sum(sizes[:i]):sum(sizes[:i + 1])] for i in range(len(sizes))]
         # wsi fc: Linear + ReLU fused in the GEMM epilogue, Dropout(0.25) in ATen (train mode only)
         h_path_bag = self.wsi_net[2](Fh.linear(x_path.float(), self.wsi_net[0].weight, self.wsi_net[0].bias, act=Fh.ACT_RELU))
-        h_omic = [_snn(self.sig_networks[i], x.float()) for i, x in enumerate(x_omic)]
-        genomics_features = torch.stack(h_omic).transpose(0, 1)                 # [B, 4, 256]
+        genomics_features = _sig_tokens(self.sig_networks, x_omic, self.training, self.snn_fused).transpose(0, 1)      # [B, 4, 256]
         pathomics_features = h_path_bag                                         # [B, n, 256]
         cls_p_enc, patch_p = self.pathomics_encoder(pathomics_features)
         cls_g_enc, patch_g = self.genomics_encoder(genomics_features)

@@ -1316,6 +1316,193 @@ def token_pool_gated(x, h2, w, b, *, scores_out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# self-normalising encoder stacks (SNN_Block, models/mcat_utils.py:81-95; MaxNet's encoder, models/model.py:142-187; csrc/snn_stack.hip):
+# up to 8 networks of up to 4 layers Linear -> ELU -> AlphaDropout, every network of a model in ONE forward launch and TWO backward launches.
+# The per-network and per-layer addresses travel as host tables (ctypes arrays, read during the call); the key sets of the two launches:
+# ------------------------------------------------------------------------------------------------
+SNN_MAX_NETS, SNN_MAX_DEPTH, SNN_MAX_WIDTH, SNN_MAX_INPUTS = 8, 4, 256, 2048
+SNN_ALPHA = 1.7580993408473766          # torch's AlphaDropout: selu's scale times its alpha
+_SNN = "x x_row_stride x_col_offset W widths keep acts out G depth B p final_relu stream "
+SNN_FWD_KEYS = frozenset((_SNN + "b").split())
+SNN_BWD_KEYS = frozenset((_SNN + "dout dz dW db dx").split())
+
+
+def _flat(v) -> list:
+    """the leaves of nested lists / tuples, in order"""
+    out = []
+    for u in v:
+        if isinstance(u, (list, tuple)):
+            out += _flat(u)
+        else:
+            out.append(u)
+    return out
+
+
+def snn_why(widths, *, rates=None, dtypes=None) -> Optional[str]:
+    """Why a group of SNN encoders stays on its composed form (linear, ELU and AlphaDropout per layer); None: it takes the fused kernels.
+    widths: one list [K_0, N_1, .., N_depth] per network.  rates: the AlphaDropout rates in force, any nesting (one rate serves the launch).
+    dtypes: the parameters' dtypes.  No GPU work."""
+    if not 1 <= len(widths) <= SNN_MAX_NETS:
+        return f"{len(widths)} networks (1 to {SNN_MAX_NETS})"
+    depth = len(widths[0]) - 1
+    if any(len(w) - 1 != depth for w in widths):
+        return f"unequal depths {[len(w) - 1 for w in widths]} (every network of a call has the same number of layers)"
+    if not 1 <= depth <= SNN_MAX_DEPTH:
+        return f"depth {depth} (1 to {SNN_MAX_DEPTH} layers)"
+    for g, w in enumerate(widths):
+        if not 1 <= w[0] <= SNN_MAX_INPUTS:
+            return f"{w[0]} inputs of network {g} (1 to {SNN_MAX_INPUTS})"
+        if not 1 <= min(w) <= max(w[1:]) <= SNN_MAX_WIDTH:
+            l = next(i for i, n in enumerate(w[1:]) if not 1 <= n <= SNN_MAX_WIDTH)
+            return f"width {w[l + 1]} of layer {l} of network {g} (1 to {SNN_MAX_WIDTH})"
+    if rates is not None:
+        rs = sorted({float(r) for r in _flat(rates)})
+        if len(rs) > 1:
+            return f"unequal dropout rates {rs} (one rate serves the launch)"
+        if rs and not 0.0 <= rs[0] < 1.0:
+            return f"dropout rate {rs[0]} (0 <= p < 1)"
+    if dtypes is not None:
+        other = sorted({str(d) for d in _flat(dtypes) if d != torch.float32})
+        if other:
+            return f"parameters of dtype {other} (the kernels are fp32)"
+    return None
+
+
+def snn_path(widths, **kw) -> str:
+    """'snn' (csrc/snn_stack.hip) or 'composed': the arguments of snn_why, which names the reason for 'composed'."""
+    return "composed" if snn_why(widths, **kw) is not None else "snn"
+
+
+def snn_keep_numel(B: int, widths) -> int:
+    """Length of the flat `keep` of snn_stack - the layout of the saved activations: dense [B, N_l] blocks in the order network 0 .. G - 1,
+    within a network layer 1 .. depth."""
+    return int(B) * sum(int(n) for w in widths for n in list(w)[1:])
+
+
+def snn_draw_keep(B: int, widths, p: float, device) -> torch.Tensor:
+    """The 0 / 1 multipliers of every layer of every network in ONE draw (bernoulli_ on one flat tensor, reproducible under
+    torch.manual_seed)."""
+    return torch.empty(snn_keep_numel(B, widths), device=device, dtype=torch.float32).bernoulli_(1.0 - float(p))
+
+
+def _snn_check(xs, weights, biases, p, keep):
+    """(G, depth, B, widths) of a call the kernels take; raises ValueError, naming the quantity, before anything is launched."""
+    if not (isinstance(xs, (list, tuple)) and isinstance(weights, (list, tuple)) and isinstance(biases, (list, tuple))) or \
+            not len(xs) == len(weights) == len(biases) or any(len(w) != len(b) for w, b in zip(weights, biases)):
+        raise ValueError("snn_stack: need one input, one list of weights and one list of biases per network")
+    widths = []
+    for g, (x, ws, bs) in enumerate(zip(xs, weights, biases)):
+        if x.dim() != 2 or any(w.dim() != 2 for w in ws) or not ws:
+            raise ValueError(f"snn_stack: network {g} needs x [B, K] and weights [N, K]")
+        w = [int(x.shape[1])]
+        for l, (W, b) in enumerate(zip(ws, bs)):
+            if W.shape[1] != w[-1] or b.numel() != W.shape[0]:
+                raise ValueError(f"snn_stack: layer {l} of network {g}: weight {tuple(W.shape)} and bias {tuple(b.shape)} do not follow {w[-1]} columns")
+            w.append(int(W.shape[0]))
+        widths.append(w)
+    why = snn_why(widths, rates=(p,), dtypes=[t.dtype for ts in (*weights, *biases) for t in ts])
+    if why is not None:
+        raise ValueError(f"snn_stack: {why}")
+    B = int(xs[0].shape[0])
+    if B < 1 or any(int(x.shape[0]) != B for x in xs):
+        raise ValueError(f"snn_stack: every network takes the same B >= 1 rows, got {[tuple(x.shape) for x in xs]}")
+    if (p > 0) != (keep is not None):
+        raise ValueError("snn_stack: keep is required with p > 0 and must be None with p = 0")
+    if keep is not None and keep.numel() != snn_keep_numel(B, widths):
+        raise ValueError(f"snn_stack: keep must hold {snn_keep_numel(B, widths)} values (snn_keep_numel), got {tuple(keep.shape)}")
+    return len(xs), len(weights[0]), B, widths
+
+
+def _snn_addrs(tensors, device):
+    """The host table of the device addresses of contiguous fp32 tensors on `device` (0 for None): the checks of capi.fptr, the device
+    looked up once by the caller"""
+    for t in tensors:
+        if t is not None and not (t.device == device and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f"smml fp32 kernels need contiguous fp32 tensors on {device}, got {t.dtype} on {t.device}, strides {t.stride()}")
+    return (C_.c_ulonglong * len(tensors))(*[0 if t is None else t.data_ptr() for t in tensors])
+
+
+def _snn_rows(t: torch.Tensor) -> torch.Tensor:
+    """The input rows as the kernels read them: fp32 on the current device with unit column stride - a column range of a wider tensor
+    stays the view it is (capi.ptr's checks without its contiguity rule)"""
+    if t.dtype != torch.float32 or not (t.stride(1) == 1 or t.shape[1] == 1) or t.stride(0) < 0:
+        t = _c(t)
+    if not t.is_cuda or t.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"smml kernels need tensors resident in the HBM of the current device, got one on {t.device}; this path has no CPU fallback")
+    return t
+
+
+class _SnnStack(torch.autograd.Function):
+    """tensors: the G inputs, then the G depth weights, then the G depth biases (network-major)"""
+
+    @staticmethod
+    def forward(ctx, keep, p, final_relu, stacked, widths, *tensors):
+        ctx.set_materialize_grads(False)
+        G, depth = len(widths), len(widths[0]) - 1
+        xs = [_snn_rows(t) for t in tensors[:G]]
+        Ws = [_c(t) for t in tensors[G:G + G * depth]]
+        bs = [_c(t) for t in tensors[G + G * depth:]]
+        B, dev = xs[0].shape[0], xs[0].device
+        keep = _c(keep).reshape(-1) if keep is not None else None
+        acts = torch.empty(snn_keep_numel(B, widths), device=dev, dtype=torch.float32)
+        last = [w[-1] for w in widths]
+        if min(last) == max(last):
+            buf = torch.empty(G, B, last[0], device=dev, dtype=torch.float32)
+            outs = [t.detach() for t in buf.unbind(0)]
+        else:
+            buf, outs = None, [torch.empty(B, n, device=dev, dtype=torch.float32) for n in last]
+        L = C_.c_longlong * G
+        offs = [x.storage_offset() for x in xs]
+        ctx.tables = dict(x=(C_.c_ulonglong * G)(*[x.data_ptr() - 4 * o for x, o in zip(xs, offs)]), x_row_stride=L(*[x.stride(0) for x in xs]),
+                          x_col_offset=L(*offs), W=_snn_addrs(Ws, dev), widths=(C_.c_int * (G * (depth + 1)))(*[n for w in widths for n in w]),
+                          out=_snn_addrs(outs, dev), G=G, depth=depth, B=B, p=p, final_relu=int(final_relu))
+        ns = dict(ctx.tables, b=_snn_addrs(bs, dev), keep=keep, acts=acts, stream=capi.stream())
+        capi.check(capi.call("smml_snn_stack_fwd_f32", ns, SNN_FWD_KEYS), "snn_stack_fwd")
+        ctx.save_for_backward(keep, acts, *xs, *Ws, *outs)
+        ctx.dims = (G, depth, stacked)
+        ctx.bias_shapes = [t.shape for t in tensors[G + G * depth:]]
+        return buf if stacked else tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        G, depth, stacked = ctx.dims
+        keep, acts, *rest = ctx.saved_tensors
+        xs, Ws = rest[:G], rest[G:G + G * depth]
+        if stacked:                                                              # one gradient [G, B, N]: its slices
+            douts = _c(douts[0]).unbind(0) if douts[0] is not None else [None] * G
+        douts = [_c(d) if d is not None else None for d in douts]
+        dev = acts.device
+        dz = torch.empty_like(acts)
+        dW = [torch.empty_like(w) for w in Ws]                                  # one allocation per parameter: autograd adopts them as they are
+        db = [torch.empty(w.shape[0], device=dev, dtype=torch.float32) for w in Ws]
+        dx = [torch.empty(x.shape, device=dev, dtype=torch.float32) if ctx.needs_input_grad[5 + g] else None for g, x in enumerate(xs)]
+        ns = dict(ctx.tables, keep=keep, acts=acts, dz=dz, dout=_snn_addrs(douts, dev), dW=_snn_addrs(dW, dev), db=_snn_addrs(db, dev),
+                  dx=_snn_addrs(dx, dev), stream=capi.stream())
+        capi.check(capi.call("smml_snn_stack_bwd_f32", ns, SNN_BWD_KEYS), "snn_stack_bwd")
+        return (None,) * 5 + tuple(dx) + tuple(dW) + tuple(t.view(s) for t, s in zip(db, ctx.bias_shapes))
+
+
+def snn_stack(xs, weights, biases, *, p: float = 0.0, keep=None, final_relu: bool = False, stacked: bool = False):
+    """G independent self-normalising encoders in one launch per direction (two backward): network g runs x_g [B, K_0] through its layers
+        e_l = ELU(a_{l-1} W_l^T + b_l)      a_l = e_l   or, with p > 0,   A keep e_l + A alpha' (keep - 1) + A alpha' p
+    (torch's AlphaDropout for the given 0 / 1 tensor, alpha' = SNN_ALPHA, A = ((alpha'^2 p + 1)(1 - p))^-1/2) and returns
+    max(a_depth, 0) with final_relu, a_depth otherwise: a tuple of one [B, N_g] tensor per network.
+    xs: one [B, K_0] tensor per network; a column range x_all[:, a:b] of a wider tensor is read in place.  weights, biases: per network the list
+    of its layers' nn.Linear parameters ([N_l, K_l] and [N_l]).  Up to 8 networks of the same depth <= 4, K_0 <= 2048, every N_l <= 256, fp32
+    parameters, one rate; anything else raises ValueError, naming the quantity, before anything is launched (snn_why tells without raising).
+    keep: ONE flat float tensor of 0 and 1 in the layout of the saved activations (snn_keep_numel; snn_draw_keep draws it in one call), drawn
+    by the caller; required with p > 0, None otherwise.
+    Where all last widths agree the returned tensors are the slices of one contiguous [G, B, N] tensor; stacked=True returns that tensor itself
+    (what torch.stack of the slices would copy).  Every weight and bias receives its gradient in a buffer of its own, the inputs only where they
+    require one.  No float atomics, one owner and one order per sum: identical bits run after run, with and without deterministic()."""
+    p = float(p)
+    G, depth, _, widths = _snn_check(xs, weights, biases, p, keep)
+    if stacked and len({w[-1] for w in widths}) != 1:
+        raise ValueError(f"snn_stack: stacked=True needs equal last widths, got {[w[-1] for w in widths]}")
+    return _SnnStack.apply(keep, p, bool(final_relu), bool(stacked), widths, *xs, *[t for ws in weights for t in ws], *[t for bs in biases for t in bs])
+
+
+# ------------------------------------------------------------------------------------------------
 # bf16-storage linear (csrc/gemm_b16.hip): x bf16 [.., K], W an fp32 parameter [N, K] -> y bf16 or fp32 [.., N]
 # ------------------------------------------------------------------------------------------------
 def _bptr(t: torch.Tensor):

@@ -11,12 +11,13 @@ few KB, where launches, not bandwidth, set the time: the 8-head self-attention i
 csrc/token_set.hip.  The bag-sized work - the wsi Linear + ReLU and the 4 genomic queries over the bag - is functional.linear and the
 few-query co-attention (csrc/fewq_attn.hip), which reads the bag once (key is value).
 
-What stays in ATen: ELU / AlphaDropout / Dropout on [B, <= 512]- and [4, B, <= 512]-sized activations, the draw of the attention-dropout
+What stays in ATen: ELU / AlphaDropout of the sig_networks (unless `snn_fused`), Dropout on [B, <= 512]- and [4, B, <= 512]-sized activations, the draw of the attention-dropout
 multipliers, stack / cat, sigmoid, cumprod.  `captum` is not mirrored.
 
 Extension key `mcat_fused` (default true): false sends the co-attention and both token-set operations through their composed forms
 (coattention.MultiheadAttention with permutes, matmul4 and softmax_rows) - the cross-check of the tests and the yardstick of
-tests/tools/bench_mcat.py.  smml.define_net does not build this class: it is delivered as an import swap."""
+tests/tools/bench_mcat.py.  Extension key `snn_fused` (default false): the four sig_networks run as one fused call
+(functional.snn_stack, csrc/snn_stack.hip) instead of a linear, an ELU and an AlphaDropout per layer.  smml.define_net does not build this class: it is delivered as an import swap."""
 from __future__ import annotations
 
 import copy
@@ -26,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import functional as Fh
-from .cmta import SNN_Block, _snn
+from .cmta import SNN_Block, _sig_tokens
 from .coattention import MultiheadAttention
 from .fusion import BilinearFusion
 
@@ -171,6 +172,11 @@ class MCAT_Surv(nn.Module):
         self.coattn.fused_few_query = self.mcat_fused
         for layer in list(self.path_transformer.layers) + list(self.omic_transformer.layers):
             layer.fused = self.mcat_fused
+        # extension key: snn_fused (absent / false: linear, ELU and AlphaDropout per layer; independent of mcat_fused) - the four sig_networks
+        # in ONE functional.snn_stack call on the column views of x_omic, whose [4, B, 256] output is the stacked tensor itself.  In train
+        # mode the dropout multipliers of all eight layers come from one draw: reproducible under torch.manual_seed, but a random stream of
+        # its own (the composed form draws once per layer)
+        self.snn_fused = bool(getattr(args, "snn_fused", False))
 
     def _pool(self, head: Attn_Net_Gated, rho: nn.Sequential, h_trans, sink=None):
         """models/model.py:633-640 / :645-651: the gated head's scores, softmax over the 4 tokens, bmm with the tokens, rho -> [B, 256]"""
@@ -196,7 +202,7 @@ class MCAT_Surv(nn.Module):
         # wsi fc: Linear + ReLU fused in the GEMM epilogue, Dropout(0.25) in ATen (train mode only); the bag stays [B, N, 256] in memory and
         # the co-attention reads its sequence-first view in place
         h_path_bag = self.wsi_net[2](Fh.linear(x_path.float(), self.wsi_net[0].weight, self.wsi_net[0].bias, act=Fh.ACT_RELU)).transpose(0, 1)
-        h_omic_bag = torch.stack([_snn(self.sig_networks[i], x.float()) for i, x in enumerate(x_omic)])       # [4, B, 256]
+        h_omic_bag = _sig_tokens(self.sig_networks, x_omic, self.training, self.snn_fused)       # [4, B, 256]
         h_path_coattn, A_coattn = self.coattn(h_omic_bag, h_path_bag, h_path_bag)          # [4, B, 256], raw scores [B, 1, 4, N]
         if sink is not None:
             sink.append(A_coattn)

@@ -17,6 +17,7 @@ from torch import nn
 from torch.nn import Parameter
 
 from . import functional as Fh
+from .cmta import _snn_fused
 from .deform_cross_trans_mil import DeformCrossTransMIL
 from .fusion import define_bifusion
 from .mil import ABMIL
@@ -46,12 +47,23 @@ class MaxNet(nn.Module):
             init_max_weights(self)
         self.output_range = Parameter(torch.FloatTensor([6]), requires_grad=False)
         self.output_shift = Parameter(torch.FloatTensor([-3]), requires_grad=False)
+        # extension (a plain attribute; define_net sets it from the key `snn_fused`): the four layers and the ReLU in ONE functional.snn_stack
+        # call instead of a linear, an ELU and an AlphaDropout per layer.  In train mode the dropout multipliers of all layers come from one
+        # draw: reproducible under torch.manual_seed, but a random stream of its own (the composed form draws once per layer)
+        self.fused = False
 
-    def forward(self, **kwargs):
-        h = kwargs['x_omic'].float()
+    def encode(self, x_omic):
+        """relu(encoder(x_omic)): the features"""
+        h = x_omic.float()
+        fused = _snn_fused([self.encoder], [h], self.training, final_relu=True) if self.fused and h.dim() == 2 else None
+        if fused is not None:
+            return fused[0]
         for blk in self.encoder:
             h = blk[2](blk[1](Fh.linear(h, blk[0].weight, blk[0].bias)))     # [B, <=64]-sized activations
-        features = self.relu(h)
+        return self.relu(h)
+
+    def forward(self, **kwargs):
+        features = self.encode(kwargs['x_omic'])
         logits = Fh.linear(features, self.classifier[0].weight, self.classifier[0].bias)
         return features, logits, None
 
@@ -87,6 +99,17 @@ class DeformPathomicNet(nn.Module):
         self.fusion_type = args.fusion_type
         self.output_range = Parameter(torch.FloatTensor([6]), requires_grad=False)
         self.output_shift = Parameter(torch.FloatTensor([-3]), requires_grad=False)
+        # extension key: snn_fused (absent / false: each MaxNet as it stands) - both omic encoders in ONE grouped functional.snn_stack call
+        self.snn_fused = bool(getattr(args, "snn_fused", False))
+
+    def _omic_vectors(self, x_tumor, x_immune):
+        """The features of the two MaxNets (their classifiers' logits are not used here): one grouped call with `snn_fused`"""
+        nets = (self.omic_net_tumor, self.omic_net_immune)
+        if self.snn_fused and x_tumor.dim() == x_immune.dim() == 2:
+            both = _snn_fused([n.encoder for n in nets], [x_tumor.float(), x_immune.float()], self.training, final_relu=True)
+            if both is not None:
+                return both
+        return self.omic_net_tumor(x_omic=x_tumor)[0], self.omic_net_immune(x_omic=x_immune)[0]
 
     def forward(self, **kwargs):
         x_path = kwargs['x_path']
@@ -97,9 +120,13 @@ class DeformPathomicNet(nn.Module):
             self.pathomic_net_tumor.prefetch(x_path.shape[1])       # parameter-only work of both branches, beside the shared first layer
             self.pathomic_net_immune.prefetch(x_path.shape[1])
             pf_t, pf_i = Fh.dual_linear_relu(x_path.float(), ft.weight, ft.bias, fi.weight, fi.bias)
-        omic_vec_tumor, _, _ = self.omic_net_tumor(x_omic=kwargs['x_omic_tumor'])
+        if self.snn_fused:
+            omic_vec_tumor, omic_vec_immune = self._omic_vectors(kwargs['x_omic_tumor'], kwargs['x_omic_immune'])
+        else:
+            omic_vec_tumor, _, _ = self.omic_net_tumor(x_omic=kwargs['x_omic_tumor'])
         rt = self.pathomic_net_tumor.forward_features(pf_t, omic_vec_tumor) if shared else self.pathomic_net_tumor(path=x_path, omic=omic_vec_tumor)
-        omic_vec_immune, _, _ = self.omic_net_immune(x_omic=kwargs['x_omic_immune'])
+        if not self.snn_fused:
+            omic_vec_immune, _, _ = self.omic_net_immune(x_omic=kwargs['x_omic_immune'])
         ri = self.pathomic_net_immune.forward_features(pf_i, omic_vec_immune) if shared else self.pathomic_net_immune(path=x_path, omic=omic_vec_immune)
         pathomic_vec_tumor, pathomic_grads_tumor = rt[0], rt[2]
         pathomic_vec_immune, pathomic_grads_immune = ri[0], ri[2]
@@ -147,12 +174,15 @@ class DeformPathomicNet(nn.Module):
 def define_net(args):
     """Modes 'deformpathomic', 'path' (ABMIL, models/mil.py:34-82) and 'omic' (a bare MaxNet) of models/model.py:49-79 (init_net with
     init_type 'max' / 'none' leaves the constructor's initialisation in place, utils/utils.py:222-240).  The extension key `abmil_gated`
-    is read by ABMIL itself: mode 'path' with it set gives the gated attention network (mil.py)."""
+    is read by ABMIL itself: mode 'path' with it set gives the gated attention network (mil.py).  The extension key `snn_fused` (absent / false:
+    the composed layers) sends the SNN encoders through functional.snn_stack: mode 'omic' sets MaxNet.fused, DeformPathomicNet reads it itself."""
     if args.mode == "path":
         return ABMIL(args)
     if args.mode == "omic":
-        return MaxNet(input_dim=args.input_size_omic, omic_dim=args.omic_dim, return_grad=args.return_grad, dropout_rate=args.dropout_rate,
-                      label_dim=args.label_dim, init_max=True if args.init_type == "max" else False)
+        net = MaxNet(input_dim=args.input_size_omic, omic_dim=args.omic_dim, return_grad=args.return_grad, dropout_rate=args.dropout_rate,
+                     label_dim=args.label_dim, init_max=True if args.init_type == "max" else False)
+        net.fused = bool(getattr(args, "snn_fused", False))
+        return net
     if args.mode != "deformpathomic":
         raise NotImplementedError(f"model [{args.mode}] is not part of the accelerated path")
     return DeformPathomicNet(args=args)
